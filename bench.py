@@ -8,13 +8,22 @@ configs[2], the configuration the metric is quoted on.
 
 One process per GPU; the batch shards on the batch axis (weak scaling: 4 volumes per GPU); the flat
 fp32 gradient buffer is all-reduced over RCCL (sum, then 1/N) before the fused optimiser step.  Inputs
-are resident in HBM before the timed region.  Prints ONE JSON line on rank 0 with the extra objects
+are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.  A plain run sets up, warms up,
+times the K steps and prints the headline figure; `--full` adds the side measurements, as the extra objects
   "roofline"           – the kernel FAMILY with the most GPU time of the step, chosen from the complete table (every launch of both streams bracketed with HIP
                          events in R instrumented steps run AFTER the timed region); "roofline_2" / "roofline_3" are the next two, "kernel_families" the table
   "other_configs"      – ms per train step of the other BASELINE.json configs and of the f32 (parity-exact) run dtype of the headline workload, 10 steps each
   "cpu_baseline"       – the oracle (torch-CPU port of the reference path) on this box's host cores
   "gpu_torch_baseline" – the same oracle functions on this GPU through stock PyTorch-ROCm / MIOpen (fp32 and autocast f16):
                          the number the hand-written engine has to beat.
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full                       # the headline figure and every side measurement
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR           # + what the last timed step computed, DIR/<name>.npy
+
+--dump-outputs: the LAST timed step starts from the seeded initial state (weights, AdamW state, loss scale, dropout stream), put back
+in an un-timed gap before it.  The kernels add floats atomically, so the state reached after many steps varies run to run in the last
+bits, and AdamW turns such bits into lr-sized weight changes; a step from the seeded state differs from run to run by rounding only, so
+two runs, and two builds, can be compared output for output (dump_outputs()).
 """
 import argparse
 import json
@@ -152,6 +161,39 @@ def other_configs(dev, steps=10):
     return out
 
 
+# --dump-outputs: per array at most this many float32 elements (20 MB), so the three large outputs stay under 64 MB together
+DUMP_MAX_ELEMS = 5000000
+
+
+def initial_state(e):
+    """the seeded state the engine starts from (weights, AdamW moments and step, loss scale, dropout stream position), for restart_from()"""
+    return e.state_dict(), e.optimizer_state_dict()
+
+
+def restart_from(e, state):
+    """--dump-outputs: put the engine back into `state` before the last timed step (un-timed), so that what that step computes depends on
+    the arguments alone and not on the float-atomic summation orders of every step before it"""
+    e.update_loss_scale(blocking=True)           # a loss-scale tally still in flight from the earlier steps is applied now, then overwritten
+    sd, opt = state
+    e.load_state_dict(sd)
+    e.load_optimizer_state_dict(opt)
+    e._steps_since_check = e._clean_steps = 0    # the host side of the loss-scale policy starts over with it
+    e.pack_weights()                             # re-packed here, so the next step takes the same launch path as every other
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """write each array as <out_dir>/<name>.npy in float32; one of more than DUMP_MAX_ELEMS elements is written flattened as the
+    DUMP_MAX_ELEMS elements at fixed positions (ascending, drawn by a generator seeded with `seed` from the element count alone)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(seed))[:DUMP_MAX_ELEMS].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -163,11 +205,16 @@ def parse(argv=None):
     ap.add_argument("--dtype", default="f16")
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--size", type=int, default=96)
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the cpu_baseline / dice_vs_ref / gpu_torch_baseline legs")
-    ap.add_argument("--roofline-steps", type=int, default=5, help="instrumented steps run AFTER the timed region: EVERY launch of the step (all kernel "
+    ap.add_argument("--full", action="store_true", help="after the headline measurement, also run the side measurements: the other_configs, "
+                    "roofline / kernel_families and cpu_baseline / dice_vs_ref / gpu_torch_baseline legs (the three options below narrow a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (loss / Dice / IoU, logits, "
+                    "probabilities, updated weights) as DIR/<name>.npy, float32, at most %d elements per array (a fixed seeded sample beyond); "
+                    "the last timed step then starts from the seeded initial state, put back in an un-timed gap before it" % DUMP_MAX_ELEMS)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline / dice_vs_ref / gpu_torch_baseline legs")
+    ap.add_argument("--roofline-steps", type=int, default=5, help="--full: instrumented steps run AFTER the timed region: EVERY launch of the step (all kernel "
                     "families, both streams) is bracketed by HIP events on its launch stream (each bracket idles the stream for ~5 us, so none of "
                     "them is inside the timed region); the family with the most GPU time is \"roofline\", the next two \"roofline_2\" / \"roofline_3\"")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the other_configs leg (the other BASELINE configs + the f32 run dtype, 10 steps each)")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the other_configs leg (the other BASELINE configs + the f32 run dtype, 10 steps each)")
     ap.add_argument("--launch", default="auto", choices=["auto", "stream", "graph"], help="how the single-rank step reaches the GPU: stream = ~250 "
                     "launches enqueued per step by one library call; graph = the step captured once as a HIP graph, one hipGraphLaunch per step; "
                     "auto = both are timed for a few steps inside the un-timed conditioning phase and the faster one runs the warm-up and the "
@@ -378,12 +425,13 @@ def _bench(a, dev, on_gpu, gpu_sync, dist, world, rank):
     S = a.size
     # the other BASELINE configs first, before anything of the headline run exists in the process: measured after the HIP-graph probe of `--launch auto`
     # the clDice config (the one path that uses a second torch stream per step) ran 11 ms instead of 6.4 (profiles/r04_bench_other_configs_order.txt)
-    others = other_configs(dev) if (on_gpu and world == 1 and rank == 0 and not a.no_other_configs) else None
+    others = other_configs(dev) if (a.full and on_gpu and world == 1 and rank == 0 and not a.no_other_configs) else None
     e = SegEngine("vnet", 3, 1, 1, dtype=a.dtype, device=dev)
     synthetic.init_engine(e, seed=0)
     if world > 1:
         from pytorchdeeplearing_amd.parallel import broadcast_parameters
         broadcast_parameters(e, src=0)          # every replica starts from rank 0's weights (the dropout streams differ per rank)
+    init = initial_state(e) if a.dump_outputs else None
     x, y = synthetic.synthetic_batch(a.batch, (S, S, S), 1, 1, seed=1234 + rank)
     x, y = x.to(dev), y.to(dev)
     logits = torch.empty((a.batch, 1, S, S, S), dtype=torch.float32, device=dev)
@@ -454,22 +502,32 @@ def _bench(a, dev, on_gpu, gpu_sync, dist, world, rank):
     gpu_sync()
     # ---- the timed region: exactly K steps, no instrumentation of any kind inside
     t0 = time.perf_counter()
-    nhost, t_enqueued = min(8, a.steps), 0.0
+    nhost, t_enqueued, t_gap = min(8, a.steps), 0.0, 0.0
     for i in range(a.steps):
+        if init is not None and i == a.steps - 1:
+            # --dump-outputs: the last timed step starts from the seeded initial state; putting it back is not timed
+            gpu_sync()
+            tg = time.perf_counter()
+            restart_from(e, init)
+            gpu_sync()
+            t_gap = time.perf_counter() - tg
         out3 = step()
         if i == nhost - 1:
-            t_enqueued = time.perf_counter() - t0      # host time to enqueue the first steps: it runs ahead of the GPU (later the full queue throttles it)
+            t_enqueued = time.perf_counter() - t0 - t_gap      # host time to enqueue the first steps: it runs ahead of the GPU (later the full queue throttles it)
     gpu_sync()
     if dist:
         dist.barrier()
     gpu_sync()
-    dt = time.perf_counter() - t0
+    dt = time.perf_counter() - t0 - t_gap
     loss = float(out3[0])
-    # ---- roofline: R instrumented steps AFTER the timed region.  EVERY launch of the step (all profile classes, main stream and weight-gradient
+    if a.dump_outputs and rank == 0:
+        # what a caller of the step receives from the last timed one: [loss, Dice, IoU], the logits / probabilities it wrote, the updated weights
+        dump_outputs(a.dump_outputs, {"loss_dice_iou": out3[:3], "logits": logits, "probs": probs, "params": e.params})
+    # ---- roofline (--full): R instrumented steps AFTER the timed region.  EVERY launch of the step (all profile classes, main stream and weight-gradient
     # stream) is bracketed with hipEventRecord on its launch stream; the classes are grouped into kernel families (FAMILIES) and the family with
     # the most GPU time is "roofline" - the choice is made from the complete table, not from a short list.
     from pytorchdeeplearing_amd import _capi
-    nprof = max(0, a.roofline_steps)
+    nprof = max(0, a.roofline_steps) if a.full else 0
     prof = {}
     if nprof:
         e.profile_enable(_capi.KERNEL_CLASSES)
@@ -488,7 +546,7 @@ def _bench(a, dev, on_gpu, gpu_sync, dist, world, rank):
     # with a timestamp.  Measured live and subtracted per launch below, so that the event-based average can be compared
     # with rocprofv3's kernel durations (which carry no brackets); both the raw and the corrected figures are reported.
     bracket_us = 0.0
-    if on_gpu:
+    if on_gpu and nprof:
         pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(200)]
         for ea, eb in pairs:
             ea.record(); eb.record()
@@ -564,13 +622,14 @@ def _bench(a, dev, on_gpu, gpu_sync, dist, world, rank):
 
         for i, name in enumerate(order[:3]):
             line["roofline" if i == 0 else "roofline_%d" % (i + 1)] = roofline_block(name, i + 1)
-        line["kernel_families"] = {k: {"queue": FAMILIES[k]["queue"], "launches_per_step": fams[k]["calls"] // nprof, "ms_per_step": round(fams[k]["ms"] / nprof, 3),
-                                       "frac": round((fams[k]["flops"] / (fams[k]["ms"] * 1e-3) / 1e12 / PEAK_MFMA_TFLOPS) if (FAMILIES[k]["bound"] == "mfma" and fams[k]["flops"] > 0)
-                                                     else (fams[k]["bytes"] / (fams[k]["ms"] * 1e-3) / 1e9 / PEAK_HBM_GBS), 4),
-                                       "bound": FAMILIES[k]["bound"]} for k in order}
+        if a.full:
+            line["kernel_families"] = {k: {"queue": FAMILIES[k]["queue"], "launches_per_step": fams[k]["calls"] // nprof, "ms_per_step": round(fams[k]["ms"] / nprof, 3),
+                                           "frac": round((fams[k]["flops"] / (fams[k]["ms"] * 1e-3) / 1e12 / PEAK_MFMA_TFLOPS) if (FAMILIES[k]["bound"] == "mfma" and fams[k]["flops"] > 0)
+                                                         else (fams[k]["bytes"] / (fams[k]["ms"] * 1e-3) / 1e9 / PEAK_HBM_GBS), 4),
+                                           "bound": FAMILIES[k]["bound"]} for k in order}
         if others is not None:
             line["other_configs"] = others
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             sd = None                      # (dice_vs_ref builds its own perturbed weights: the trained ones predict a trivial mask)
             del e
             if on_gpu:

@@ -341,11 +341,45 @@ def make_prepost():
     np.savez_compressed(os.path.join(OUT, "prepost.npz"), **out)
 
 
+REF_MODULES = (("VNet3d", (1, 1)), ("UNet3d", (1, 4)), ("VNet2d", (1, 2)), ("UNet2d", (3, 1)))        # module tree
+REF_INITS = (("VNet3d", (1, 1)), ("UNet3d", (1, 4)), ("VNet2d", (3, 2)), ("UNet2d", (1, 1)))          # initialize_weights, seed 100 + index
+REF_SKIPPED_LEAVES = ("ReLU", "Dropout3d", "Dropout2d", "MaxPool3d", "MaxPool2d")                     # parameter-free leaves the engine folds away
+
+
+def tensor_sha256(t):
+    import hashlib
+    return hashlib.sha256(t.detach().cpu().float().contiguous().numpy().tobytes()).hexdigest()
+
+
+def make_reference_modules(nets):
+    """the reference networks' state_dict layout, leaf module order and seeded `initialize_weights` values (as SHA-256 of the float32 bytes
+    of each tensor) -> tests/golden/reference_modules.json"""
+    import json
+    out = {"tree": [], "init": []}
+    for cls, args in REF_MODULES:
+        m = getattr(nets, cls)(*args)
+        sd = m.state_dict()
+        out["tree"].append({"cls": cls, "args": list(args), "keys": list(sd.keys()), "shapes": [list(v.shape) for v in sd.values()],
+                            "leaves": [type(x).__name__ for x in m.modules() if not list(x.children()) and type(x).__name__ not in REF_SKIPPED_LEAVES]})
+    for seed, (cls, args) in enumerate(REF_INITS):
+        m = getattr(nets, cls)(*args)
+        torch.manual_seed(100 + seed)
+        m.apply(nets.initialize_weights)
+        out["init"].append({"cls": cls, "args": list(args), "seed": 100 + seed,
+                            "sha256": {k: tensor_sha256(v) for k, v in m.state_dict().items()}})
+    with open(os.path.join(OUT, "reference_modules.json"), "w") as f:
+        json.dump(out, f, indent=1)
+    print("reference modules:", [(t["cls"], len(t["keys"])) for t in out["tree"]])
+
+
 def main():
     if not ref_loader.available():
         sys.exit("reference tree not available; golden fixtures can only be regenerated in the build container")
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(1)
+    if "--only-reference-modules" in sys.argv:
+        make_reference_modules(ref_loader.load()[0])
+        return
     if "--only-metric-extra" in sys.argv:
         _nets, _losses, metric = ref_loader.load()
         make_metric_extra(metric)

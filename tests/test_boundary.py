@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import ref_loader, seg_oracle as seg
+from oracle import seg_oracle as seg
 from pytorchdeeplearing_amd import losses, metric, networks
 
 
@@ -211,43 +211,51 @@ def test_module_boundary(dev, cls, kind, ndim, args, shape):
     assert not torch.equal(t1, l1) and not torch.equal(t1, t2)
 
 
-@pytest.mark.skipif(not ref_loader.available(), reason="reference tree only exists in the build container")
-def test_module_tree_matches_live_reference():
-    nets, _, _ = ref_loader.load()
+def _reference_modules(golden_dir):
+    """the reference networks' state_dict layout, leaf module order and seeded `initialize_weights` values, recorded from the reference
+    itself (oracle/make_golden.py, make_reference_modules)"""
+    import json
+    with open(os.path.join(golden_dir, "reference_modules.json")) as f:
+        return json.load(f)
+
+
+def test_module_tree_matches_live_reference(golden_dir):
     from tests.conftest import emu_library
     emu_library()
-    for ours, theirs in ((networks.VNet3d(1, 1), nets.VNet3d(1, 1)), (networks.UNet3d(1, 4), nets.UNet3d(1, 4)),
-                         (networks.VNet2d(1, 2), nets.VNet2d(1, 2)), (networks.UNet2d(3, 1), nets.UNet2d(3, 1))):
-        a, b = ours.state_dict(), theirs.state_dict()
-        assert list(a.keys()) == list(b.keys())
-        assert all(a[k].shape == b[k].shape for k in a)
-        # same leaf module types in the same order -> model.apply(initialize_weights) visits them identically
+    recs = _reference_modules(golden_dir)["tree"]
+    assert [(r["cls"], tuple(r["args"])) for r in recs] == [("VNet3d", (1, 1)), ("UNet3d", (1, 4)), ("VNet2d", (1, 2)), ("UNet2d", (3, 1))]
+    for rec in recs:
+        ours = getattr(networks, rec["cls"])(*rec["args"])
+        a = ours.state_dict()
+        assert list(a.keys()) == rec["keys"]
+        assert [list(v.shape) for v in a.values()] == rec["shapes"]
+        # same leaf module types in the same order -> model.apply(initialize_weights) visits them identically (the reference's parameter-free
+        # ReLU / dropout / max-pool leaves are left out of the record)
         ta = [type(m).__name__ for m in ours.modules() if not list(m.children())]
-        tb = [type(m).__name__ for m in theirs.modules() if not list(m.children()) and type(m).__name__ not in ("ReLU", "Dropout3d", "Dropout2d", "MaxPool3d", "MaxPool2d")]
-        assert ta == tb
+        assert ta == rec["leaves"]
 
 
-@pytest.mark.skipif(not ref_loader.available(), reason="reference tree only exists in the build container")
-def test_initialize_weights_draws_the_reference_values():
-    """A9 (networks/__init__.py:11-26) at the VALUE level: the same seed followed by `apply(initialize_weights)` gives the live reference
+def test_initialize_weights_draws_the_reference_values(golden_dir):
+    """A9 (networks/__init__.py:11-26) at the VALUE level: the same seed followed by `apply(initialize_weights)` gives the reference
     module and this package's module identical state_dicts (same leaf order, same fan computation, same RNG consumption) - what makes a
-    training run started here reproduce a run started on the reference."""
-    nets, _, _ = ref_loader.load()
+    training run started here reproduce a run started on the reference.  The reference's tensors are recorded as SHA-256 of their bytes."""
+    from oracle.make_golden import tensor_sha256
     from tests.conftest import emu_library
     emu_library()
-    for seed, (ours, theirs) in enumerate(((networks.VNet3d(1, 1, dtype="f32"), nets.VNet3d(1, 1)), (networks.UNet3d(1, 4, dtype="f32"), nets.UNet3d(1, 4)),
-                                           (networks.VNet2d(3, 2, dtype="f32"), nets.VNet2d(3, 2)), (networks.UNet2d(1, 1, dtype="f32"), nets.UNet2d(1, 1)))):
-        torch.manual_seed(100 + seed)
-        theirs.apply(nets.initialize_weights)
-        torch.manual_seed(100 + seed)
+    recs = _reference_modules(golden_dir)["init"]
+    assert [(r["cls"], tuple(r["args"]), r["seed"]) for r in recs] == [("VNet3d", (1, 1), 100), ("UNet3d", (1, 4), 101), ("VNet2d", (3, 2), 102),
+                                                                        ("UNet2d", (1, 1), 103)]
+    for rec in recs:
+        ours = getattr(networks, rec["cls"])(*rec["args"], dtype="f32")
+        torch.manual_seed(rec["seed"])
         ours.apply(networks.initialize_weights)
-        a, b = ours.state_dict(), theirs.state_dict()
-        assert list(a.keys()) == list(b.keys())
+        a = ours.state_dict()
+        assert list(a.keys()) == list(rec["sha256"].keys())
         for k in a:
-            assert torch.equal(a[k].cpu(), b[k]), k
+            assert tensor_sha256(a[k]) == rec["sha256"][k], k
         # and the values really are in the engine's flat buffer (the views alias it), not in detached copies
         w0 = next(iter(a))
-        assert torch.equal(ours.engine.param_view(w0).cpu().reshape(b[w0].shape), b[w0])
+        assert tensor_sha256(ours.engine.param_view(w0).reshape(a[w0].shape)) == rec["sha256"][w0]
 
 
 @pytest.mark.parametrize("shape,c", [((2, 1, 5, 6, 7), 1), ((3, 4, 9, 11), 4), ((1, 3, 4, 4, 6), 3)])

@@ -7,7 +7,7 @@ cd /root/repo; mkdir -p gpurun_out; export TMPDIR=/tmp
 TAG=${1:-final}; O=gpurun_out/$TAG; mkdir -p $O
 python -c "from pytorchdeeplearing_amd import _capi; print(_capi.product_library().build_info())" > $O/build.txt 2>&1; cat $O/build.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -3 $O/smoke.log
-DRV="python bench.py --gpus 1 --steps 20 --warmup 5"
+DRV="python bench.py --gpus 1 --steps 20 --warmup 5 --full"
 SHORT="python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs --roofline-steps 0 --condition-seconds 0 --launch stream"
 rm -rf gpurun_out/pmc gpurun_out/pmc_sq gpurun_out/prof gpurun_out/trace gpurun_out/prof32
 for c in FETCH_SIZE WRITE_SIZE; do
