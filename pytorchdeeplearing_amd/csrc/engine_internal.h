@@ -57,6 +57,7 @@ struct Step {
     int x_fwd = -1, x_dg0 = -1, x_dg1 = -1;   // conv3x tiling of the forward / data-gradient launches (-1: conv3_kernel, row-major weights)
     int draw = -1;           // gradient wrt raw
     bool dual_dg = false;    // 1^d conv on a concat: both data-gradients come from one streaming launch (seg_conv_args.out1)
+    bool rq_dg = false;      // ... and that launch also leaves the GroupNorm-backward sums of vact_unit (set together with rq_fused of the ACT step it reads)
     int vact_unit = -1;      // >= 0: in0 is the (never written) activation of that UNIT step: this conv and its weight gradient read the unit's RAW output and apply
                              // GroupNorm + dropout + ReLU on load (conv_stream_kernel / wgrad_direct_kernel <..., ACT>)
     // ACT
