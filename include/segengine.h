@@ -471,6 +471,23 @@ int seg_cldice_target(const void* target, int label_type, int n, int d, int h, i
 int seg_cldice_binary(const float* probs, const void* target, int label_type, int n, int d, int h, int w, int nd, int width,
                       float grad_scale, void* ws, float* out1, float* dlogits, int target_ready, void* stream);
 
+/* ---- Seg_Metirc3d (model/metric.py:11-142) on the device: the four overlap counts and the symmetric surface distances of two label volumes
+ * [d][h][w] (uint8) in one call (csrc/surface.hip).  A voxel belongs to the mask when label == cls, or when label != 0 for cls == -1 (the
+ * reference's binary case).  Surface = mask voxels with one of their 18 neighbours outside the mask or outside the volume (binary_erosion with
+ * generate_binary_structure(3, 2), border_value 0); nearest distances by an exact all-pairs search with the spacing (sz, sy, sx) of the (d, h, w) axes
+ * rounded to f32.  out16 (device memory, 16 doubles) = {|R|, |P|, |R n P|, |R u P|, n_surf_R, n_surf_P, sum r2p, sum p2r, sum r2p^2, sum p2r^2,
+ * max r2p, max p2r, 0, 0, 0, 0}; with an empty surface on either side the six counts are still correct and the six distance fields are NaN.
+ * real2pred_nn / pred2real_nn: NULL, or room for d*h*w floats each; they receive the per-point distances in raster order of the surface points.
+ * ws: seg_surface_ws_bytes() bytes, 256-byte aligned, sized for the case that every voxel is a surface voxel (a checkerboard): 16.3 bytes per voxel
+ * (four uint32 per voxel, two ballot bits per voxel, 32 bytes per 4096 voxels) + 13 KB.  After the call ws holds the packed linear indices
+ * ((z*h + y)*w + x, uint32, raster order) of the real surface at byte 0 and of the pred surface at byte 256*ceil(4*d*h*w / 256).
+ * Limits: 1 <= d, h, w <= 2048 and d*h*w < 2^31 (with unit spacing every squared distance is then an integer f32 holds exactly).
+ * No allocation, no host synchronisation, no grid that depends on a count; two calls on the same input agree bit for bit. */
+long long seg_surface_ws_bytes(int d, int h, int w);
+int seg_surface_metrics(const unsigned char* real, const unsigned char* pred, int d, int h, int w, int cls,
+                        double sz, double sy, double sx, void* ws, double* out16,
+                        float* real2pred_nn, float* pred2real_nn, void* stream);
+
 /* ---- measurement: HIP-event timing of kernel classes inside a running forward/backward.
  * seg_profile_enable(h, mask): from now on every launch whose class bit is set in `mask` is
  * bracketed by hipEventRecord on the launch stream (0 disables).  seg_profile_read(h, ...)

@@ -171,6 +171,23 @@ int seg_metric(const float* probs, const void* target, int label_type, int n, in
     return hipGetLastError() == hipSuccess ? 0 : fail("seg_metric: launch failed");
 }
 
+
+static int surface_extents_ok(int d, int h, int w) {
+    return d >= 1 && h >= 1 && w >= 1 && d <= 2048 && h <= 2048 && w <= 2048 && (long long)d * h * w < (1ll << 31);
+}
+long long seg_surface_ws_bytes(int d, int h, int w) {
+    if (!surface_extents_ok(d, h, w)) return fail("seg_surface_ws_bytes: extents must be 1..2048 with d*h*w < 2^31");
+    return (long long)surface_ws_bytes(d, h, w);
+}
+int seg_surface_metrics(const unsigned char* real, const unsigned char* pred, int d, int h, int w, int cls, double sz, double sy, double sx, void* ws,
+                        double* out16, float* real2pred_nn, float* pred2real_nn, void* stream) {
+    if (!real || !pred || !ws || !out16) return fail("seg_surface_metrics: null pointer");
+    if (!surface_extents_ok(d, h, w)) return fail("seg_surface_metrics: extents must be 1..2048 with d*h*w < 2^31");
+    if (cls < -1 || cls > 255) return fail("seg_surface_metrics: cls must be -1 (label != 0) or a label value 0..255");
+    launch_surface_metrics(real, pred, d, h, w, cls, sz, sy, sx, ws, out16, real2pred_nn, pred2real_nn, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : fail("seg_surface_metrics: launch failed");
+}
+
 }  // extern "C"
 namespace segi {
 // riders: the overflow flag was cleared and the step counter will be advanced by StepRiders of neighbouring launches (seg_train_step)

@@ -241,6 +241,11 @@ int launch_ssim_backward(const float* x1, const float* x2, int N, int C, int D, 
 
 // dice / iou on probabilities (model/metric.py): out2 = {dice, iou}; sums = 3*N*C doubles (zeroed by the launcher)
 void launch_metric(const float* probs, const void* target, int label_type, int N, int C, long long V, double* sums, float* out2, hipStream_t s);
+// Seg_Metirc3d (model/metric.py:11-142), surface.hip: label volumes [D][H][W] u8, mask = (label == cls) or (label != 0) for cls == -1;
+// out16 / ws / nn arrays as documented at seg_surface_metrics in include/segengine.h
+size_t surface_ws_bytes(int D, int H, int W);
+void launch_surface_metrics(const unsigned char* real, const unsigned char* pred, int D, int H, int W, int cls, double sz, double sy, double sx, void* ws,
+                            double* out16, float* real2pred_nn, float* pred2real_nn, hipStream_t s);
 // out[c] += sum_m x[m][c]   (bias gradient of a conv without GroupNorm)
 void launch_colsum(const void* x, float* out, long long M, int C, int dtype, hipStream_t s);
 
