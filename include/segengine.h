@@ -488,6 +488,31 @@ int seg_surface_metrics(const unsigned char* real, const unsigned char* pred, in
                         double sz, double sy, double sx, void* ws, double* out16,
                         float* real2pred_nn, float* pred2real_nn, void* stream);
 
+/* ---- ImageDataGenerator3D (dataprocess/Augmentation/images_masks_3dtransform.py:63-269) on the device: a batch of images and their label volumes
+ * through per-sample affine transforms in ONE launch (csrc/augment.hip) - scipy.ndimage.affine_transform(order = 0) per channel in the reference.
+ * x / out: f32, n samples of c channels on the grid (n0, n1, n2); element (s, ch, i0, i1, i2) lives at s*c*V + ch*xs_c + ((i0*n1 + i1)*n2 + i2)*xs_v with
+ * V = n0*n1*n2, so (N, C, D, H, W) is (xs_c, xs_v) = (V, 1) and the reference's channel-last (N, n0, n1, n2, C) is (1, c).  out != x, same layout.
+ * label / label_out: NULL, or SEG_LABEL_U8 / _I64 / _F32 volumes on the same grid with label_c channels: 1 (no channel axis), or c (the image's strides).
+ * params_dev: device memory, SEG_AUGMENT_PARAM_DOUBLES doubles per sample: [0..8] the 3x3 matrix A row-major, [9..11] the offset, [12] the flips
+ * (1: axis 0, 2: axis 1, 4: axis 2, or-ed), [16 + ch] the channel shift u_ch (read by seg_augment3d_shift, ch < 8), the rest 0.  params_host: the same block
+ * in host memory; it is only validated (finite matrix and offset, flips 0..7) and need not outlive the call - uploading it is the caller's business.
+ * Output voxel o = (i0, i1, i2) takes the input voxel at floor(cc_a + 0.5) per axis a, cc_a = ((i0*A[a][0] + i1*A[a][1]) + i2*A[a][2]) + off[a] in double
+ * without fused multiply-add; SEG_AUGMENT_NEAREST clamps cc_a to [0, n_a - 1], SEG_AUGMENT_CONSTANT gives cval (label: label_cval) to a voxel with any
+ * cc_a < 0 or cc_a > n_a - 1.  The value is stored at the flipped position of o.  rescale != 0: out = v * (float)rescale (image only).  extrema != 0:
+ * instead of rescaling, the minimum and maximum of every transformed sample (all channels) are left in ws for seg_augment3d_shift.
+ * seg_augment3d_shift (in place, same layout arguments): x = clip(x + (float)u_ch, min, max) when params_dev != NULL (needs c <= 8 and the ws of a
+ * seg_augment3d call with extrema != 0 on the same stream), then x *= (float)rescale when rescale != 0.
+ * ws: seg_augment3d_ws_bytes(n) bytes (256 per sample), 256-byte aligned.  Errors (nothing is launched): null pointers, n outside 1..65535, an extent
+ * below 1 or n0*n1*n2 above 2^31, a non-finite matrix / offset / cval, SEG_AUGMENT_REFLECT / _WRAP (not implemented), a label_cval an integer label type
+ * cannot hold (mode constant).  Stream-ordered, no allocation, no readback, no synchronisation; no parameter value can make a read leave the input. */
+enum { SEG_AUGMENT_NEAREST = 0, SEG_AUGMENT_CONSTANT = 1, SEG_AUGMENT_REFLECT = 2, SEG_AUGMENT_WRAP = 3, SEG_AUGMENT_PARAM_DOUBLES = 24 };
+long long seg_augment3d_ws_bytes(int n);
+int seg_augment3d(const float* x, float* out, int n, int c, int n0, int n1, int n2, long long xs_c, long long xs_v,
+                  const void* label, void* label_out, int label_type, int label_c, const double* params_host, const double* params_dev,
+                  int fill_mode, double cval, double label_cval, double rescale, int extrema, void* ws, void* stream);
+int seg_augment3d_shift(float* x, int n, int c, int n0, int n1, int n2, long long xs_c, long long xs_v, const double* params_dev,
+                        double rescale, const void* ws, void* stream);
+
 /* ---- measurement: HIP-event timing of kernel classes inside a running forward/backward.
  * seg_profile_enable(h, mask): from now on every launch whose class bit is set in `mask` is
  * bracketed by hipEventRecord on the launch stream (0 disables).  seg_profile_read(h, ...)

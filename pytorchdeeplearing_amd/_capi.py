@@ -105,6 +105,9 @@ SIGNATURES = {
     "seg_cldice_binary": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp]),
     "seg_surface_ws_bytes": (_ll, [_i, _i, _i]),
     "seg_surface_metrics": (_i, [_vp, _vp, _i, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp, _vp]),
+    "seg_augment3d_ws_bytes": (_ll, [_i]),
+    "seg_augment3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _ll, _ll, _vp, _vp, _i, _i, _vp, _vp, _i, _d, _d, _d, _i, _vp, _vp]),
+    "seg_augment3d_shift": (_i, [_vp, _i, _i, _i, _i, _i, _ll, _ll, _vp, _d, _vp, _vp]),
     "seg_op_resample3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, _d, _d, _i, _vp]),
     "seg_op_normalize_ws_bytes": (_ll, []),
     "seg_op_normalize_meanstd": (_i, [_vp, _vp, _ll, _i, _f, _f, _vp, _vp]),

@@ -1,5 +1,7 @@
 // The stateless entry points of include/segengine.h: losses, metrics, optimiser, pre / post-processing and the operator-level seg_op_* calls the
 // tests and tools use.  Nothing here touches an engine handle.
+#include <cmath>
+
 #include "engine_internal.h"
 
 extern "C" {
@@ -186,6 +188,68 @@ int seg_surface_metrics(const unsigned char* real, const unsigned char* pred, in
     if (cls < -1 || cls > 255) return fail("seg_surface_metrics: cls must be -1 (label != 0) or a label value 0..255");
     launch_surface_metrics(real, pred, d, h, w, cls, sz, sy, sx, ws, out16, real2pred_nn, pred2real_nn, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? 0 : fail("seg_surface_metrics: launch failed");
+}
+
+
+static int augment_extents_ok(int n, int c, int n0, int n1, int n2) {
+    return n >= 1 && n <= 65535 && c >= 1 && c <= 65535 && n0 >= 1 && n1 >= 1 && n2 >= 1 && (long long)n0 * n1 <= (1ll << 31) &&
+           (long long)n0 * n1 * n2 <= (1ll << 31);
+}
+// the last element of a sample, (c - 1)*xs_c + (V - 1)*xs_v, lies inside its c*V elements: (V, 1), (1, c) and nothing that reaches further
+static int augment_strides_ok(int c, long long V, long long xs_c, long long xs_v) {
+    return xs_c >= 1 && xs_v >= 1 && xs_c <= V && xs_v <= c && (c - 1) * xs_c + (V - 1) * xs_v < (long long)c * V;
+}
+long long seg_augment3d_ws_bytes(int n) {
+    if (n < 1 || n > 65535) return fail("seg_augment3d_ws_bytes: n must be 1..65535");
+    return (long long)augment3d_ws_bytes(n);
+}
+int seg_augment3d(const float* x, float* out, int n, int c, int n0, int n1, int n2, long long xs_c, long long xs_v, const void* label, void* label_out,
+                  int label_type, int label_c, const double* params_host, const double* params_dev, int fill_mode, double cval, double label_cval,
+                  double rescale, int extrema, void* ws, void* stream) {
+    if (!x || !out || x == out || !params_host || !params_dev || !ws || (label != nullptr) != (label_out != nullptr) || (label && label == label_out))
+        return fail("seg_augment3d: null pointer, or a transform in place");
+    if (!augment_extents_ok(n, c, n0, n1, n2)) return fail("seg_augment3d: n, c must be 1..65535, extents >= 1 with n0*n1*n2 <= 2^31");
+    if (!augment_strides_ok(c, (long long)n0 * n1 * n2, xs_c, xs_v)) return fail("seg_augment3d: strides must be positive and stay inside a sample's c*V elements");
+    if (fill_mode == SEG_AUGMENT_REFLECT || fill_mode == SEG_AUGMENT_WRAP)
+        return fail("seg_augment3d: fill modes reflect and wrap are not implemented (nearest and constant are)");
+    if (fill_mode != SEG_AUGMENT_NEAREST && fill_mode != SEG_AUGMENT_CONSTANT) return fail("seg_augment3d: unknown fill mode");
+    if (label && label_type != LT_U8 && label_type != LT_I64 && label_type != LT_F32) return fail("seg_augment3d: label type must be u8, i64 or f32");
+    if (label && label_c != 1 && label_c != c) return fail("seg_augment3d: label_c must be 1 or c");
+    if (extrema && c > 8) return fail("seg_augment3d: a channel shift needs c <= 8");
+    if (!std::isfinite(cval) || !std::isfinite(label_cval) || !std::isfinite(rescale)) return fail("seg_augment3d: cval / rescale must be finite");
+    for (int s = 0; s < n; ++s) {
+        const double* p = params_host + (size_t)s * SEG_AUGMENT_PARAM_DOUBLES;
+        for (int k = 0; k < 12; ++k)
+            if (!std::isfinite(p[k])) return fail("seg_augment3d: non-finite matrix or offset");
+        if (!(p[12] >= 0.0 && p[12] <= 7.0) || p[12] != (double)(int)p[12]) return fail("seg_augment3d: flips must be an integer 0..7");
+    }
+    if (label && fill_mode == SEG_AUGMENT_CONSTANT && label_type != LT_F32) {
+        const double lim = label_type == LT_U8 ? 255.0 : 9007199254740992.0;      // (2^53: every integer below is a double)
+        if (label_cval != std::floor(label_cval) || label_cval > lim || label_cval < (label_type == LT_U8 ? 0.0 : -lim))
+            return fail("seg_augment3d: label_cval is not representable in the label type");
+    }
+    Augment3dArgs a = {};
+    a.x = x; a.out = out; a.label = label; a.label_out = label_out; a.params = params_dev;
+    a.N = n; a.C = c; a.LC = label ? label_c : 0; a.n0 = n0; a.n1 = n1; a.n2 = n2;
+    a.V = (long long)n0 * n1 * n2; a.xs_c = xs_c; a.xs_v = xs_v;
+    a.ls_c = label_c == 1 ? 0 : xs_c; a.ls_v = label_c == 1 ? 1 : xs_v;
+    a.constant = fill_mode == SEG_AUGMENT_CONSTANT; a.cval = (float)cval; a.label_cval = label_cval;
+    a.extrema = extrema != 0;
+    a.has_scale = !a.extrema && rescale != 0.0; a.scale = (float)rescale;
+    launch_augment3d(a, label_type, ws, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : fail("seg_augment3d: launch failed");
+}
+int seg_augment3d_shift(float* x, int n, int c, int n0, int n1, int n2, long long xs_c, long long xs_v, const double* params_dev, double rescale,
+                        const void* ws, void* stream) {
+    if (!x || (params_dev && !ws)) return fail("seg_augment3d_shift: null pointer");
+    if (!augment_extents_ok(n, c, n0, n1, n2)) return fail("seg_augment3d_shift: n, c must be 1..65535, extents >= 1 with n0*n1*n2 <= 2^31");
+    if (!augment_strides_ok(c, (long long)n0 * n1 * n2, xs_c, xs_v))
+        return fail("seg_augment3d_shift: strides must be positive and stay inside a sample's c*V elements");
+    if (params_dev && c > 8) return fail("seg_augment3d_shift: a channel shift needs c <= 8");
+    if (!std::isfinite(rescale)) return fail("seg_augment3d_shift: rescale must be finite");
+    if (!params_dev && rescale == 0.0) return 0;
+    launch_augment3d_shift(x, n, c, (long long)n0 * n1 * n2, xs_c, xs_v, params_dev, ws, (float)rescale, rescale != 0.0, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : fail("seg_augment3d_shift: launch failed");
 }
 
 }  // extern "C"

@@ -246,6 +246,26 @@ void launch_metric(const float* probs, const void* target, int label_type, int N
 size_t surface_ws_bytes(int D, int H, int W);
 void launch_surface_metrics(const unsigned char* real, const unsigned char* pred, int D, int H, int W, int cls, double sz, double sy, double sx, void* ws,
                             double* out16, float* real2pred_nn, float* pred2real_nn, hipStream_t s);
+// ImageDataGenerator3D (dataprocess/Augmentation/images_masks_3dtransform.py), augment.hip: one gather launch per batch + the in-place channel-shift /
+// rescale pass; parameter block, strides and workspace as documented at seg_augment3d in include/segengine.h
+constexpr int AUG_PARAM_DOUBLES = SEG_AUGMENT_PARAM_DOUBLES;
+constexpr int AUG_EXTREMA_REP = 32;
+struct Augment3dArgs {
+    const float* x; float* out;                  // [N] samples of C channels on the grid (n0, n1, n2): element = n*C*V + c*xs_c + voxel*xs_v
+    const void* label; void* label_out;          // nullptr, or LC channels (1, or C with the image's strides)
+    const double* params;                        // device, [N][AUG_PARAM_DOUBLES]
+    unsigned* ws_min; unsigned* ws_max;          // set by the launcher
+    int N, C, LC, n0, n1, n2;
+    long long V, xs_c, xs_v, ls_c, ls_v;
+    int constant; float cval; double label_cval; // fill mode constant: voxels whose coordinate leaves [0, n - 1] get cval
+    float scale; int has_scale;                  // out = v * scale in the gather pass (not together with extrema)
+    int extrema;                                 // collect min / max of the transformed image per sample into the workspace
+};
+size_t augment3d_ws_bytes(int N);
+void launch_augment3d(Augment3dArgs a, int label_type, void* ws, hipStream_t s);
+// in place: clip(x + (float)params[n][16 + c], min, max) from the workspace when params != nullptr, then * scale when has_scale
+void launch_augment3d_shift(float* x, int N, int C, long long V, long long xs_c, long long xs_v, const double* params, const void* ws, float scale,
+                            int has_scale, hipStream_t s);
 // out[c] += sum_m x[m][c]   (bias gradient of a conv without GroupNorm)
 void launch_colsum(const void* x, float* out, long long M, int C, int dtype, hipStream_t s);
 

@@ -19,6 +19,9 @@ so here:
     (np.load, `.long()`, collate, narrowing, pin_memory - the last one a fresh pinned allocation per batch), which is what it takes to feed a
     GPU that trains ~1000 volumes/s from the page cache (tools/bench_pipeline.py, profiles/r04_pipeline_end_to_end.json).
 
+  * `augment=gen` (an `ImageDataGenerator3D`, pytorchdeeplearing_amd/augment.py) transforms every 3-D batch on the device between the upload and the
+    step: the random affine transform, flips, channel shift and rescale of the reference's offline `DataAug3D`, one launch per batch.
+
 Yields (x float32 (N,C,...) contiguous, y uint8/int64 (N,...) contiguous) on `device`, in DataLoader order."""
 import os
 import queue
@@ -55,8 +58,9 @@ class _PinnedPool:
 
 
 class DevicePrefetcher:
-    def __init__(self, loader, device, binary, depth=2, workers=None):
+    def __init__(self, loader, device, binary, depth=2, workers=None, augment=None):
         self.loader, self.device, self.binary, self.depth = loader, torch.device(device), binary, max(1, int(depth))
+        self.augment = augment                           # an ImageDataGenerator3D (pytorchdeeplearing_amd/augment.py) or None
         self.cuda = self.device.type == "cuda"
         self.copy_stream = torch.cuda.Stream(self.device) if self.cuda else None
         if workers is None:
@@ -206,9 +210,23 @@ class DevicePrefetcher:
 
     def _ready(self, p):
         if not self.cuda:
-            return p[0], p[1]
+            return (p[0], p[1]) if self.augment is None else self._augment(p[0], p[1])
         xd, yd, ev = p[0], p[1], p[2]
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(ev)                                 # stream-side wait: the host does not block
         xd.record_stream(cur); yd.record_stream(cur)
-        return xd, yd
+        return (xd, yd) if self.augment is None else self._augment(xd, yd)
+
+    def _augment(self, xd, yd):
+        """on-device augmentation of a 3-D batch as it is handed out: one draw per sample in sample order (global np.random, on the consumer's thread),
+        the parameters staged in a recycled pinned buffer and uploaded without blocking, one gather launch on the consumer's stream.
+        x (N, C, D, H, W): axes 0, 1, 2 of the generator = D, H, W, as DataAug3D maps them."""
+        from ..augment import PARAM_DOUBLES
+        buf = self.pool.take((xd.shape[0], PARAM_DOUBLES), torch.float64)
+        xa, ya = self.augment.augment_batch(xd, yd, layout="th", params_buffer=buf)
+        ev = None
+        if self.cuda:
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.device))
+        self.pool.give(buf, ev)                            # reusable once its upload has completed
+        return xa, ya

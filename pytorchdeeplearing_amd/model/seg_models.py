@@ -39,6 +39,7 @@ class _SegModel(object):
     _focal_gamma = 2
     _mask_scale = 255      # BinaryUNet3dModel.predict returns *1 (modelUnet.py:678)
     _norm3d = "meanstd"    # VNet wrappers z-score (modelVNet.py:681); UNet wrappers use percentile normalize
+    augment = None         # an ImageDataGenerator3D: trainprocess transforms every TRAINING batch on the device (pytorchdeeplearing_amd/augment.py)
 
     def _init(self, dims, image_channel, numclass, batch_size, loss_name, inference, model_path, use_cuda):
         self.batch_size, self.loss_name, self.accuracyname = batch_size, loss_name, "dice"
@@ -128,7 +129,7 @@ class _SegModel(object):
             tl, ta, vl, va = [], [], [], []
             trainshow = True
             # reader thread + pinned staging + copy stream; labels binarised / narrowed to uint8 on the host (model/pipeline.py)
-            for x, y in DevicePrefetcher(train_loader, self.device, self._binary):
+            for x, y in DevicePrefetcher(train_loader, self.device, self._binary, augment=self.augment):
                 out3 = eng.train_step(x, y, self.loss_name, lr=lr, weight_decay=wd, decoupled=self._adamw, focal_alpha=0.25,
                                       focal_gamma=fgamma, class_alpha=class_alpha, mask_mode=_capi.MASKS_RANDOM).clone()
                 if trainshow:
