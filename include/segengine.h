@@ -513,6 +513,41 @@ int seg_augment3d(const float* x, float* out, int n, int c, int n0, int n1, int 
 int seg_augment3d_shift(float* x, int n, int c, int n0, int n1, int n2, long long xs_c, long long xs_v, const double* params_dev,
                         double rescale, const void* ws, void* stream);
 
+/* ---- mask post-processing (dataprocess/utils.py:7-96 of the reference) on the device (csrc/postproc.hip): connected components and binary morphology
+ * of n independent uint8 volumes [n][d][h][w] (2-D: d = 1).  A voxel is foreground when value == cls, or when value != 0 for cls == -1.  Nothing
+ * connects or spreads across samples.  Limits: 1 <= d, h, w <= 2048, 1 <= n <= 65535, n*d*h*w < 2^31.
+ *
+ * seg_cc_label.  connectivity 1: faces (6 neighbours, 4 for d = 1; ITK's ConnectedComponent and scipy.ndimage.label default); 3: fully connected (26 / 8).
+ * labels: NULL, or n*d*h*w int32: 0 for background, components numbered 1..K per sample in raster order (x fastest) of each component's first voxel -
+ * scipy.ndimage.label's numbering.  stats: device memory, SEG_CC_STATS_INTS int32 per sample:
+ *   [0] K   [1] foreground voxels   [2] size of the largest component   [3] its label number   [4] in-sample linear index (z*h + y)*w + x of its first voxel
+ *   [5..10] inclusive bounding box z0 y0 x0 z1 y1 x1 of the largest component   [11..16] the same of the whole foreground   [17..31] 0
+ * An empty foreground gives K 0, size 0, label 0, index -1 and boxes {d, h, w, -1, -1, -1}.  Of several largest components the one whose first voxel
+ * comes first in raster order is taken (a loop with `maxsize < size` over ascending labels keeps the same one).
+ * seg_cc_filter.  SEG_CC_KEEP_LARGEST: out = the input value where the voxel belongs to the largest component, else 0; SEG_CC_MIN_SIZE: the same for every
+ * component of at least min_voxels voxels.  out may be mask; stats may be NULL.  The decision is taken on the device, nothing is read back.
+ * ws: seg_cc_ws_bytes() bytes, 256-byte aligned: 12 bytes per voxel (parent, root and size per voxel slot) + 20 bytes per 64-voxel row word + 160 per sample.
+ *
+ * seg_morph3d.  out = fg_value where the result is set, else 0; out may be mask.  op: SEG_MORPH_*; shape with per-axis radii 0..31: SEG_SE_BOX the full
+ * (2r+1) cuboid, SEG_SE_CROSS the three axis segments, SEG_SE_BALL the offsets with sum_a (delta_a / (r_a + 0.5))^2 <= 1 over the axes with r_a > 0 and
+ * delta_a = 0 on the others (ITK's FlatStructuringElement::Ball with a non-parametric radius as published: 19 voxels for (1,1,1), 81 for (2,2,2), 179 for
+ * (3,3,3), 9 for (0,1,1)).  border: the value assumed outside the volume, 0 or 1; -1 = 0 for a dilation, 1 for an erosion.  SEG_MORPH_OPEN =
+ * dilate(erode(x, 1), 0), SEG_MORPH_CLOSE = erode(dilate(x, 0), 1); they take border -1 only.  Equal to scipy.ndimage.binary_dilation / binary_erosion
+ * with structure = the element and border_value = border.  ws: seg_morph3d_ws_bytes() bytes (two bit planes), 256-byte aligned.
+ *
+ * All calls: stream-ordered, no allocation, no host synchronisation, no grid that depends on the data, integer arithmetic only - two calls on the same
+ * input agree bit for bit.  Errors (nothing is launched, seg_last_error() says which): null pointers, limits, a connectivity other than 1 or 3, unknown
+ * mode / op / shape, a radius outside 0..31, an explicit border with open / close, fg_value outside 0..255. */
+enum { SEG_CC_STATS_INTS = 32, SEG_CC_KEEP_LARGEST = 0, SEG_CC_MIN_SIZE = 1 };
+enum { SEG_MORPH_DILATE = 0, SEG_MORPH_ERODE = 1, SEG_MORPH_OPEN = 2, SEG_MORPH_CLOSE = 3, SEG_SE_BALL = 0, SEG_SE_BOX = 1, SEG_SE_CROSS = 2 };
+long long seg_cc_ws_bytes(int n, int d, int h, int w);
+int seg_cc_label(const unsigned char* mask, int n, int d, int h, int w, int cls, int connectivity, void* ws, int* labels, int* stats, void* stream);
+int seg_cc_filter(const unsigned char* mask, unsigned char* out, int n, int d, int h, int w, int cls, int connectivity, int mode,
+                  long long min_voxels, void* ws, int* stats, void* stream);
+long long seg_morph3d_ws_bytes(int n, int d, int h, int w);
+int seg_morph3d(const unsigned char* mask, unsigned char* out, int n, int d, int h, int w, int cls, int op, int shape, int rz, int ry, int rx,
+                int border, int fg_value, void* ws, void* stream);
+
 /* ---- measurement: HIP-event timing of kernel classes inside a running forward/backward.
  * seg_profile_enable(h, mask): from now on every launch whose class bit is set in `mask` is
  * bracketed by hipEventRecord on the launch stream (0 disables).  seg_profile_read(h, ...)

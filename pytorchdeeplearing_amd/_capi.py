@@ -108,6 +108,11 @@ SIGNATURES = {
     "seg_augment3d_ws_bytes": (_ll, [_i]),
     "seg_augment3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _ll, _ll, _vp, _vp, _i, _i, _vp, _vp, _i, _d, _d, _d, _i, _vp, _vp]),
     "seg_augment3d_shift": (_i, [_vp, _i, _i, _i, _i, _i, _ll, _ll, _vp, _d, _vp, _vp]),
+    "seg_cc_ws_bytes": (_ll, [_i, _i, _i, _i]),
+    "seg_cc_label": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "seg_cc_filter": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _ll, _vp, _vp, _vp]),
+    "seg_morph3d_ws_bytes": (_ll, [_i, _i, _i, _i]),
+    "seg_morph3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "seg_op_resample3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, _d, _d, _i, _vp]),
     "seg_op_normalize_ws_bytes": (_ll, []),
     "seg_op_normalize_meanstd": (_i, [_vp, _vp, _ll, _i, _f, _f, _vp, _vp]),

@@ -252,6 +252,53 @@ int seg_augment3d_shift(float* x, int n, int c, int n0, int n1, int n2, long lon
     return hipGetLastError() == hipSuccess ? 0 : fail("seg_augment3d_shift: launch failed");
 }
 
+
+static int postproc_extents_ok(int n, int d, int h, int w) {
+    return n >= 1 && n <= 65535 && d >= 1 && h >= 1 && w >= 1 && d <= 2048 && h <= 2048 && w <= 2048 && (long long)n * d * h * w < (1ll << 31);
+}
+static const char* const POSTPROC_EXTENTS = "n must be 1..65535, extents 1..2048 with n*d*h*w < 2^31";
+long long seg_cc_ws_bytes(int n, int d, int h, int w) {
+    if (!postproc_extents_ok(n, d, h, w)) return fail(std::string("seg_cc_ws_bytes: ") + POSTPROC_EXTENTS);
+    return (long long)cc_ws_bytes(n, d, h, w);
+}
+int seg_cc_label(const unsigned char* mask, int n, int d, int h, int w, int cls, int connectivity, void* ws, int* labels, int* stats, void* stream) {
+    if (!mask || !ws || !stats) return fail("seg_cc_label: null pointer");
+    if (!postproc_extents_ok(n, d, h, w)) return fail(std::string("seg_cc_label: ") + POSTPROC_EXTENTS);
+    if (cls < -1 || cls > 255) return fail("seg_cc_label: cls must be -1 (value != 0) or a value 0..255");
+    if (connectivity != 1 && connectivity != 3) return fail("seg_cc_label: connectivity must be 1 (faces) or 3 (fully connected)");
+    launch_cc_label(mask, n, d, h, w, cls, connectivity, ws, labels, stats, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : fail("seg_cc_label: launch failed");
+}
+int seg_cc_filter(const unsigned char* mask, unsigned char* out, int n, int d, int h, int w, int cls, int connectivity, int mode, long long min_voxels,
+                  void* ws, int* stats, void* stream) {
+    if (!mask || !out || !ws) return fail("seg_cc_filter: null pointer");
+    if (!postproc_extents_ok(n, d, h, w)) return fail(std::string("seg_cc_filter: ") + POSTPROC_EXTENTS);
+    if (cls < -1 || cls > 255) return fail("seg_cc_filter: cls must be -1 (value != 0) or a value 0..255");
+    if (connectivity != 1 && connectivity != 3) return fail("seg_cc_filter: connectivity must be 1 (faces) or 3 (fully connected)");
+    if (mode != SEG_CC_KEEP_LARGEST && mode != SEG_CC_MIN_SIZE) return fail("seg_cc_filter: unknown mode");
+    if (mode == SEG_CC_MIN_SIZE && min_voxels < 0) return fail("seg_cc_filter: min_voxels must not be negative");
+    launch_cc_filter(mask, out, n, d, h, w, cls, connectivity, mode, min_voxels, ws, stats, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : fail("seg_cc_filter: launch failed");
+}
+long long seg_morph3d_ws_bytes(int n, int d, int h, int w) {
+    if (!postproc_extents_ok(n, d, h, w)) return fail(std::string("seg_morph3d_ws_bytes: ") + POSTPROC_EXTENTS);
+    return (long long)morph3d_ws_bytes(n, d, h, w);
+}
+int seg_morph3d(const unsigned char* mask, unsigned char* out, int n, int d, int h, int w, int cls, int op, int shape, int rz, int ry, int rx, int border,
+                int fg_value, void* ws, void* stream) {
+    if (!mask || !out || !ws) return fail("seg_morph3d: null pointer");
+    if (!postproc_extents_ok(n, d, h, w)) return fail(std::string("seg_morph3d: ") + POSTPROC_EXTENTS);
+    if (cls < -1 || cls > 255) return fail("seg_morph3d: cls must be -1 (value != 0) or a value 0..255");
+    if (op < SEG_MORPH_DILATE || op > SEG_MORPH_CLOSE) return fail("seg_morph3d: unknown operation");
+    if (shape < SEG_SE_BALL || shape > SEG_SE_CROSS) return fail("seg_morph3d: unknown structuring element");
+    if (rz < 0 || ry < 0 || rx < 0 || rz > 31 || ry > 31 || rx > 31) return fail("seg_morph3d: radii must be 0..31");
+    if (border < -1 || border > 1) return fail("seg_morph3d: border must be 0, 1 or -1 (the operation's default)");
+    if ((op == SEG_MORPH_OPEN || op == SEG_MORPH_CLOSE) && border != -1) return fail("seg_morph3d: open and close take no explicit border");
+    if (fg_value < 0 || fg_value > 255) return fail("seg_morph3d: fg_value must be 0..255");
+    launch_morph3d(mask, out, n, d, h, w, cls, op, shape, rz, ry, rx, border, fg_value, ws, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : fail("seg_morph3d: launch failed");
+}
+
 }  // extern "C"
 namespace segi {
 // riders: the overflow flag was cleared and the step counter will be advanced by StepRiders of neighbouring launches (seg_train_step)

@@ -266,6 +266,15 @@ void launch_augment3d(Augment3dArgs a, int label_type, void* ws, hipStream_t s);
 // in place: clip(x + (float)params[n][16 + c], min, max) from the workspace when params != nullptr, then * scale when has_scale
 void launch_augment3d_shift(float* x, int N, int C, long long V, long long xs_c, long long xs_v, const double* params, const void* ws, float scale,
                             int has_scale, hipStream_t s);
+// mask post-processing (dataprocess/utils.py:7-96), postproc.hip: n uint8 volumes [D][H][W], foreground = (value == cls) or (value != 0) for cls == -1;
+// connected components and binary morphology on the bit-packed rows; arguments, stats and workspaces as documented at seg_cc_label / seg_morph3d
+size_t cc_ws_bytes(int n, int d, int h, int w);
+void launch_cc_label(const unsigned char* mask, int n, int d, int h, int w, int cls, int connectivity, void* ws, int* labels, int* stats, hipStream_t s);
+void launch_cc_filter(const unsigned char* mask, unsigned char* out, int n, int d, int h, int w, int cls, int connectivity, int mode, long long min_voxels,
+                      void* ws, int* stats, hipStream_t s);
+size_t morph3d_ws_bytes(int n, int d, int h, int w);
+void launch_morph3d(const unsigned char* mask, unsigned char* out, int n, int d, int h, int w, int cls, int op, int shape, int rz, int ry, int rx, int border,
+                    int fg_value, void* ws, hipStream_t s);
 // out[c] += sum_m x[m][c]   (bias gradient of a conv without GroupNorm)
 void launch_colsum(const void* x, float* out, long long M, int C, int dtype, hipStream_t s);
 

@@ -40,6 +40,8 @@ class _SegModel(object):
     _mask_scale = 255      # BinaryUNet3dModel.predict returns *1 (modelUnet.py:678)
     _norm3d = "meanstd"    # VNet wrappers z-score (modelVNet.py:681); UNet wrappers use percentile normalize
     augment = None         # an ImageDataGenerator3D: trainprocess transforms every TRAINING batch on the device (pytorchdeeplearing_amd/augment.py)
+    postprocess = None     # callable, device uint8 (D, H, W) -> device uint8 (D, H, W): the 3-D inference / inference_patch mask on the source grid passes
+                           # through it before it leaves the device, e.g. functools.partial(prepost.keep_largest_component) (None changes nothing)
 
     def _init(self, dims, image_channel, numclass, batch_size, loss_name, inference, model_path, use_cuda):
         self.batch_size, self.loss_name, self.accuracyname = batch_size, loss_name, "dice"
@@ -220,6 +222,14 @@ class _SegModel(object):
         out.SetOrigin(image_sitk.GetOrigin()); out.SetSpacing(image_sitk.GetSpacing()); out.SetDirection(image_sitk.GetDirection())
         return out
 
+    def _postprocessed(self, mask):
+        if self.postprocess is None:
+            return mask
+        out = self.postprocess(mask)
+        if not torch.is_tensor(out) or out.dtype != torch.uint8 or out.shape != mask.shape or out.device != mask.device:
+            raise TypeError("postprocess must map a device uint8 mask to a device uint8 mask of the same shape")
+        return out
+
     def inference(self, image, newSize=(96, 96, 96)):
         if self._ndim == 2:
             # modelVNet.py:231-242: resize, /255, predict, resize the mask back
@@ -243,7 +253,7 @@ class _SegModel(object):
             else:
                 resized = PP.normalize_percentile(resized)                    # normalize(.)
             mask = self._predict_device(resized[None, None])[0]
-            final = PP.resample3d(mask.reshape(grid), arr.shape, mode=PP.NEAREST).cpu().numpy()
+            final = self._postprocessed(PP.resample3d(mask.reshape(grid), arr.shape, mode=PP.NEAREST)).cpu().numpy()
         return self._like(image_sitk, final)
 
     def inference_patch(self, image, newSpacing=(0.5, 0.5, 0.5), spacing=None):
@@ -272,7 +282,7 @@ class _SegModel(object):
             final = torch.zeros(arr.shape, dtype=torch.uint8, device=self.device)
             m = [min(a, b) for a, b in zip(arr.shape, back_size)]
             final[:m[0], :m[1], :m[2]] = back[:m[0], :m[1], :m[2]]
-            final = final.cpu().numpy().astype(arr.dtype)          # np.zeros_like(source array) (modelUnet.py:752)
+            final = self._postprocessed(final).cpu().numpy().astype(arr.dtype)          # np.zeros_like(source array) (modelUnet.py:752)
         return self._like(image_sitk, final)
 
     def clear_GPU_cache(self):

@@ -118,3 +118,104 @@ def stitch_mask(masks, origins, out):
     lib.check(lib.seg_op_stitch_mask(masks.data_ptr(), origins.data_ptr(), nb, *pshape, out.data_ptr(), *out.shape,
                                      _capi.stream_for(out.device)), "seg_op_stitch_mask")
     return out
+
+
+# ---- mask post-processing (dataprocess/utils.py:7-96): connected components and binary morphology, csrc/postproc.hip ----
+
+CC_STATS = 32                # int32 per sample: K, foreground voxels, largest size, its label, its first voxel, its box (6), the foreground box (6), zeros
+KEEP_LARGEST, MIN_SIZE = 0, 1
+MORPH_OPS = {"dilate": 0, "erode": 1, "open": 2, "close": 3}
+SE_SHAPES = {"ball": 0, "box": 1, "cross": 2}
+_pp_ws = {}                  # (device, stream) -> the largest workspace asked for so far
+
+
+def _pp_workspace(device, nbytes):
+    key = (str(device), _capi.stream_for(device).value)
+    ws = _pp_ws.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _pp_ws[key] = aligned_empty(nbytes, device)
+    return ws
+
+
+def _pp_mask(mask):
+    """device uint8 (D, H, W) or (N, D, H, W) -> (contiguous tensor, (n, d, h, w))"""
+    if not torch.is_tensor(mask) or mask.dtype != torch.uint8 or mask.dim() not in (3, 4):
+        raise TypeError("expected a uint8 tensor (D, H, W) or (N, D, H, W)")
+    mask = mask.contiguous()
+    return mask, ((1,) + tuple(mask.shape) if mask.dim() == 3 else tuple(mask.shape))
+
+
+def _pp_out(mask, out):
+    if out is None:
+        return torch.empty_like(mask)
+    if out.dtype != torch.uint8 or out.shape != mask.shape or out.device != mask.device or not out.is_contiguous():
+        raise ValueError("out must be a contiguous uint8 tensor of the mask's shape on its device")
+    return out
+
+
+def _pp_cls(cls):
+    return -1 if cls is None else int(cls)
+
+
+def connected_components(mask, connectivity=1, cls=None, labels=True):
+    """Components of the voxels equal to `cls` (None: non-zero) per sample; connectivity 1 = faces, 3 = fully connected.  Returns (labels int32 of the
+    mask's shape, numbered 1..K like scipy.ndimage.label; stats int32 (N, 32), see seg_cc_label in include/segengine.h)."""
+    mask, nd = _pp_mask(mask)
+    lib = _capi.lib_for(mask.device)
+    nbytes = lib.seg_cc_ws_bytes(*nd)
+    lib.check(nbytes, "seg_cc_ws_bytes")
+    ws = _pp_workspace(mask.device, nbytes)
+    lab = torch.empty(mask.shape, dtype=torch.int32, device=mask.device) if labels else None
+    stats = torch.empty((nd[0], CC_STATS), dtype=torch.int32, device=mask.device)
+    lib.check(lib.seg_cc_label(mask.data_ptr(), *nd, _pp_cls(cls), int(connectivity), ws.data_ptr(), lab.data_ptr() if labels else None,
+                               stats.data_ptr(), _capi.stream_for(mask.device)), "seg_cc_label")
+    return lab, stats
+
+
+def _cc_filter(mask, mode, min_voxels, connectivity, cls, out):
+    mask, nd = _pp_mask(mask)
+    out = _pp_out(mask, out)
+    lib = _capi.lib_for(mask.device)
+    nbytes = lib.seg_cc_ws_bytes(*nd)
+    lib.check(nbytes, "seg_cc_ws_bytes")
+    ws = _pp_workspace(mask.device, nbytes)
+    lib.check(lib.seg_cc_filter(mask.data_ptr(), out.data_ptr(), *nd, _pp_cls(cls), int(connectivity), mode, int(min_voxels), ws.data_ptr(), None,
+                                _capi.stream_for(mask.device)), "seg_cc_filter")
+    return out
+
+
+def keep_largest_component(mask, connectivity=1, cls=None, out=None):
+    """the input value on the largest component of every sample (ties: the first in raster order), 0 elsewhere; out may be mask"""
+    return _cc_filter(mask, KEEP_LARGEST, 0, connectivity, cls, out)
+
+
+def remove_small_components(mask, min_voxels, connectivity=1, cls=None, out=None):
+    """the input value on the components of at least min_voxels voxels, 0 elsewhere; out may be mask"""
+    return _cc_filter(mask, MIN_SIZE, min_voxels, connectivity, cls, out)
+
+
+def foreground_bbox(mask, cls=None):
+    """int32 (N, 6) (or (6,) for a (D, H, W) mask) on the device: inclusive z0 y0 x0 z1 y1 x1 of the foreground; {D, H, W, -1, -1, -1} when there is none"""
+    _, stats = connected_components(mask, 1, cls, labels=False)
+    box = stats[:, 11:17]
+    return box[0] if mask.dim() == 3 else box
+
+
+def binary_morphology(mask, op, radius, shape="ball", border=None, fg_value=1, cls=None, out=None):
+    """dilate / erode / open / close of the voxels equal to `cls` (None: non-zero) with a ball, box or cross of `radius` (an int or (rz, ry, rx));
+    border = the value outside the volume (None: 0 for a dilation, 1 for an erosion); result fg_value / 0.  scipy.ndimage.binary_dilation /
+    binary_erosion with that structure and border_value; out may be mask."""
+    mask, nd = _pp_mask(mask)
+    out = _pp_out(mask, out)
+    if op not in MORPH_OPS or shape not in SE_SHAPES:
+        raise ValueError("op must be one of %s and shape one of %s" % (sorted(MORPH_OPS), sorted(SE_SHAPES)))
+    r = (int(radius),) * 3 if np.isscalar(radius) else tuple(int(v) for v in radius)
+    if len(r) != 3:
+        raise ValueError("radius must be an int or (rz, ry, rx)")
+    lib = _capi.lib_for(mask.device)
+    nbytes = lib.seg_morph3d_ws_bytes(*nd)
+    lib.check(nbytes, "seg_morph3d_ws_bytes")
+    ws = _pp_workspace(mask.device, nbytes)
+    lib.check(lib.seg_morph3d(mask.data_ptr(), out.data_ptr(), *nd, _pp_cls(cls), MORPH_OPS[op], SE_SHAPES[shape], *r, -1 if border is None else int(border),
+                              int(fg_value), ws.data_ptr(), _capi.stream_for(mask.device)), "seg_morph3d")
+    return out
