@@ -427,8 +427,65 @@ int seg_op_conv3x_default_cfg(int ndim, int n, int d, int h, int wid, int cin, i
 /* seg_pack_desc.frag of the weights tiling `cfg` reads: 1, 2 (Cin == 16) or 3 (Cin == 16, 3-D tilings 28 .. 31: the halo fragments are reused across
  * the kh taps, csrc/conv3x_impl.h conv3x16r_kernel); 0 for an unknown id */
 int seg_op_conv3x_cfg_frag(int cfg);
-/* sizeof of the structs of this header as compiled into the library: 0 conv, 1 wgrad, 2 pack, 3 stemx, 4 train */
+/* sizeof of the structs of this header as compiled into the library: 0 conv, 1 wgrad, 2 pack, 3 stemx, 4 train, 5 gn_fwd, 6 gn_bwd */
 int seg_abi_sizeof(int which);
+
+/* ---- GroupNorm(8) + channel dropout + ReLU (+ second branch, + residual) and max-pool, one operator at a time (csrc/norm.hip, csrc/misc.hip):
+ * the launches the engine issues, with the path named by the caller.  A path whose own eligibility rule says no is an error and nothing is launched.
+ * Tensors [N][V][C] in the run dtype, C in {16, 32, 64, 128, 256}; statistics `stats` [32][N][C][2] fp64 = per-channel {sum r, sum r^2}, spread over the
+ * first `rep` (1..32) replicas, the other replicas zero; gamma / beta [C]; mask [N][mask_ld] dropout multipliers or null.
+ *   out = relu(scale1 * r1 + shift1) [+ relu(scale2 * r2 + shift2)] [+ res],  scale = mask * gamma * rstd,  shift = mask * (beta - gamma * mean * rstd)
+ * scale / shift [N][C] and mean / rstd [N][8] are outputs.  The second branch (r2 != null) has its own statistics, parameters and outputs. */
+enum { SEG_GN_FWD_FINALIZE = 0,   /* gn_finalize launch, then the elementwise pass */
+       SEG_GN_FWD_FOLD = 1,       /* the elementwise pass folds the statistics itself */
+       SEG_GN_FWD_GROUP = 2 };    /* one workgroup per (sample, group): seg_op_gn_group_eligible, no second branch */
+typedef struct seg_gn_fwd_args {
+    const void* r1; const void* r2; const void* res; void* out;
+    const double* stats1; const double* stats2;
+    const float* gamma1; const float* beta1; const float* gamma2; const float* beta2;
+    const float* mask1; const float* mask2; int mask_ld;
+    float* scale1; float* shift1; float* mean1; float* rstd1;
+    float* scale2; float* shift2; float* mean2; float* rstd2;
+    int N, C; long long V;
+    float eps; int rep; int path;
+} seg_gn_fwd_args;
+int seg_op_gn_forward(const seg_gn_fwd_args* a, int dtype, void* stream);
+/* The backward of the same unit.  Gradient sources: ndy (0..3) stored tensors dy[i] plus the optional virtual head source
+ * dy[n][v][c] += sum_k vdl[n][k][v] * vw[k][c] (vdl planar fp32 [N][vK][V], vw [vK][C]); dz = (their sum) * [scale * r + shift > 0].
+ * scale / shift / mean / rstd / stats / gamma / mask: as the forward left them (inputs).  Q [32][N][C][2] fp64 must be ZERO at the call:
+ * the reduce launch leaves {sum dz, sum dz * r} spread over its first rep_q replicas, the co-operative kernel uses it as its exchange area
+ * ([N][8][S][C/8] words of two floats).  coef [N][C][3] = (A, B, Cc) (written by the first two paths), dr = A * dz + B * r + Cc;
+ * dgamma / dbeta / dbias [C] fp32 are accumulated into (dbias may be null).  A second branch (r2 != null: its own scale2 .. dr2, fed by the same
+ * gradient sources) exists on the first two paths only. */
+enum { SEG_GN_BWD_SEPARATE = 0,   /* reduce, finalize, apply: three launches */
+       SEG_GN_BWD_FOLD = 1,       /* reduce, then an apply launch that folds the finalize */
+       SEG_GN_BWD_GROUP = 2,      /* one workgroup per (sample, group): seg_op_gn_group_eligible, stored sources only */
+       SEG_GN_BWD_COOP = 3 };     /* S workgroups per (sample, group): seg_op_gn_coop_plan, 1..3 stored sources only */
+typedef struct seg_gn_bwd_args {
+    const void* dy[3]; int ndy;
+    const float* vdl; const float* vw; int vK;
+    const void* r; const void* r2;
+    const float* scale; const float* shift; const float* scale2; const float* shift2;
+    const float* mean; const float* rstd; const float* mean2; const float* rstd2;
+    const double* stats; const double* stats2;
+    const float* gamma; const float* gamma2;
+    const float* mask; const float* mask2; int mask_ld;
+    double* Q; double* Q2;
+    float* coef; float* coef2;
+    void* dr; void* dr2;
+    float* dgamma; float* dbeta; float* dbias;
+    float* dgamma2; float* dbeta2; float* dbias2;
+    int N, C; long long V;
+    int rep_q, rep_s; int path;
+} seg_gn_bwd_args;
+int seg_op_gn_backward(const seg_gn_bwd_args* a, int dtype, void* stream);
+/* the co-operative kernel's plan for a shape (esz: bytes per element): 1 and *S workgroups per (sample, group), *ku chunks per thread; 0: not eligible */
+int seg_op_gn_coop_plan(int c, long long v, int n, int esz, int* S, int* ku);
+int seg_op_gn_group_eligible(int c, long long v, int esz);
+/* max-pool with window = stride = (pd, ph, pw), each 1 or 2 and a divisor of its extent, on [N][D][H][W][C] (C % 8 == 0).  backward = 0: out = pool(in);
+ * backward = 1: din (fine) = dout (coarse) routed to the first maximum of each window of `in` in (d, h, w) scan order, zero elsewhere. */
+int seg_op_maxpool(const void* in, void* out, const void* dout, void* din, int n, int d, int h, int w, int c, int pd, int ph, int pw,
+                   int backward, int dtype, void* stream);
 
 /* ---- soft-clDice building blocks (model/lossescldice.py:5-59; corrected restatement).
  * Planar fp32 tensors [planes][D][H][W]; nd = 3 pools 3x3x3 over (D,H,W), nd = 2 pools 3x3 over (H,W); stride 1, pad 1,

@@ -91,6 +91,11 @@ SIGNATURES = {
     "seg_op_stemx_partial_bytes": (_ll, [_i, _i, _i, _i, _i, _i]),
     "seg_op_stemx": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "seg_abi_sizeof": (_i, [_i]),
+    "seg_op_gn_forward": (_i, [_vp, _i, _vp]),
+    "seg_op_gn_backward": (_i, [_vp, _i, _vp]),
+    "seg_op_gn_coop_plan": (_i, [_i, _ll, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "seg_op_gn_group_eligible": (_i, [_i, _ll, _i]),
+    "seg_op_maxpool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "seg_op_pool3": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "seg_op_skel_iter": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "seg_op_skel_iter_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
@@ -148,11 +153,21 @@ class SegLib:
     def __init__(self, path):
         self.path = path
         self.dll = C.CDLL(path)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(self.dll, name)     # raises AttributeError when the symbol is missing
-            fn.restype = res
-            fn.argtypes = args
-            setattr(self, name, fn)
+
+    def __getattr__(self, name):
+        """An entry point is bound at its first use, so a library built from an older tree still serves the entries it has; one it lacks
+        raises AttributeError at the call that needs it (never a fall-back).  `bind_all` is the whole-header check of build()."""
+        if name not in SIGNATURES:
+            raise AttributeError(name)
+        fn = getattr(self.dll, name)         # raises AttributeError when the symbol is missing
+        fn.restype, fn.argtypes = SIGNATURES[name]
+        setattr(self, name, fn)
+        return fn
+
+    def bind_all(self):
+        for name in SIGNATURES:
+            getattr(self, name)
+        return self
 
     def check(self, rc, what=""):
         if rc is not None and rc < 0:
@@ -172,7 +187,7 @@ def product_library():
             raise RuntimeError(
                 "libsegengine.so (gfx950) is not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `python -m pytorchdeeplearing_amd.build`. There is no CPU fallback.")
-        _product = SegLib(LIB_PATH)
+        _product = SegLib(LIB_PATH).bind_all()      # the product library carries every entry of the header
     return _product
 
 

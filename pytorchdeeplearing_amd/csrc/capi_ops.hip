@@ -422,7 +422,125 @@ int seg_op_stemx(const seg_stemx_args* a, int mode, int ndim, int dtype, float* 
 }
 int seg_abi_sizeof(int which) {
     return which == 0 ? (int)sizeof(seg_conv_args) : which == 1 ? (int)sizeof(seg_wgrad_args) : which == 2 ? (int)sizeof(seg_pack_desc)
-           : which == 3 ? (int)sizeof(seg_stemx_args) : (int)sizeof(seg_train_args);
+           : which == 3 ? (int)sizeof(seg_stemx_args) : which == 5 ? (int)sizeof(seg_gn_fwd_args) : which == 6 ? (int)sizeof(seg_gn_bwd_args)
+           : (int)sizeof(seg_train_args);
+}
+
+// ---- GroupNorm + dropout + ReLU and max-pool at operator level: the engine's launches (engine_plan.hip: fwd_act, bwd_act, bwd_act_dual) with the path
+// named by the caller
+}  // extern "C"
+namespace segi {
+static const char* gn_shape_error(int N, int C, long long V, int dtype) {
+    if (dtype < DT_F32 || dtype > DT_BF16) return "unknown dtype";
+    if (C != 16 && C != 32 && C != 64 && C != 128 && C != 256) return "C must be 16, 32, 64, 128 or 256";
+    if (N < 1 || N > 65535 || V < 1) return "N must be 1..65535 and V >= 1";
+    if (V * (C / 8) >= (1ll << 31) || (long long)N * V * (C / 8) >= (1ll << 31)) return "tensor too large (chunk index in 32 bits)";
+    return nullptr;
+}
+}  // namespace segi
+extern "C" {
+int seg_op_gn_forward(const seg_gn_fwd_args* a, int dtype, void* stream) {
+    if (!a || !a->r1 || !a->out || !a->stats1 || !a->gamma1 || !a->beta1 || !a->scale1 || !a->shift1 || !a->mean1 || !a->rstd1)
+        return fail("seg_op_gn_forward: null pointer");
+    if (a->r2 && (!a->stats2 || !a->gamma2 || !a->beta2 || !a->scale2 || !a->shift2 || !a->mean2 || !a->rstd2))
+        return fail("seg_op_gn_forward: null pointer (second branch)");
+    if (const char* e = gn_shape_error(a->N, a->C, a->V, dtype)) return fail(std::string("seg_op_gn_forward: ") + e);
+    if (a->rep < 1 || a->rep > STAT_REP) return fail("seg_op_gn_forward: rep must be 1..32");
+    if ((a->mask1 || a->mask2) && a->mask_ld < a->C) return fail("seg_op_gn_forward: mask_ld must be >= C");
+    if (a->path < SEG_GN_FWD_FINALIZE || a->path > SEG_GN_FWD_GROUP) return fail("seg_op_gn_forward: unknown path");
+    const int esz = dtype == DT_F32 ? 4 : 2;
+    GnFinArgs f1{}, f2{};
+    f1.stats = a->stats1; f1.gamma = a->gamma1; f1.beta = a->beta1; f1.mask = a->mask1; f1.mask_ld = a->mask_ld;
+    f1.scale = a->scale1; f1.shift = a->shift1; f1.mean = a->mean1; f1.rstd = a->rstd1;
+    f1.N = a->N; f1.C = a->C; f1.V = a->V; f1.eps = a->eps; f1.rep = a->rep;
+    f2 = f1;
+    f2.stats = a->stats2; f2.gamma = a->gamma2; f2.beta = a->beta2; f2.mask = a->mask2;
+    f2.scale = a->scale2; f2.shift = a->shift2; f2.mean = a->mean2; f2.rstd = a->rstd2;
+    hipStream_t st = (hipStream_t)stream;
+    if (a->path == SEG_GN_FWD_GROUP) {
+        if (a->r2) return fail("seg_op_gn_forward: the one-workgroup-per-group form has no second branch");
+        if (!gn_bwd_group_eligible(a->C, a->V, esz)) return fail("seg_op_gn_forward: shape not eligible for the one-workgroup-per-group form (C >= 64, <= 128 KB per sample)");
+        launch_gn_fwd_group(f1, a->r1, a->res, a->out, dtype, st);
+        return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_gn_forward: launch failed");
+    }
+    ActArgs x{};
+    x.r1 = a->r1; x.scale1 = a->scale1; x.shift1 = a->shift1;
+    if (a->r2) { x.r2 = a->r2; x.scale2 = a->scale2; x.shift2 = a->shift2; }
+    x.res = a->res; x.out = a->out; x.N = a->N; x.C = a->C; x.V = a->V;
+    if (a->path == SEG_GN_FWD_FOLD) {
+        x.fold = 1; x.fin1 = f1;
+        if (a->r2) x.fin2 = f2;
+    } else if (a->r2) launch_gn_finalize(f1, st, &f2);
+    else launch_gn_finalize(f1, st);
+    launch_gn_act(x, dtype, st);
+    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_gn_forward: launch failed");
+}
+
+int seg_op_gn_backward(const seg_gn_bwd_args* a, int dtype, void* stream) {
+    if (!a || !a->r || !a->scale || !a->shift || !a->mean || !a->rstd || !a->stats || !a->gamma || !a->Q || !a->dr || !a->dgamma || !a->dbeta)
+        return fail("seg_op_gn_backward: null pointer");
+    if (a->r2 && (!a->scale2 || !a->shift2 || !a->mean2 || !a->rstd2 || !a->stats2 || !a->gamma2 || !a->Q2 || !a->dr2 || !a->dgamma2 || !a->dbeta2))
+        return fail("seg_op_gn_backward: null pointer (second branch)");
+    if (a->ndy < 0 || a->ndy > 3 || (a->ndy == 0 && !a->vdl)) return fail("seg_op_gn_backward: 1..3 stored gradient sources, or a virtual one");
+    for (int i = 0; i < a->ndy; ++i)
+        if (!a->dy[i]) return fail("seg_op_gn_backward: null pointer (gradient source)");
+    if (a->vdl && (!a->vw || a->vK < 1 || a->vK > 16)) return fail("seg_op_gn_backward: the virtual source needs vw and vK in 1..16");
+    if (const char* e = gn_shape_error(a->N, a->C, a->V, dtype)) return fail(std::string("seg_op_gn_backward: ") + e);
+    if (a->rep_q < 1 || a->rep_q > STAT_REP || a->rep_s < 1 || a->rep_s > STAT_REP) return fail("seg_op_gn_backward: rep_q / rep_s must be 1..32");
+    if ((a->mask || a->mask2) && a->mask_ld < a->C) return fail("seg_op_gn_backward: mask_ld must be >= C");
+    if (a->path < SEG_GN_BWD_SEPARATE || a->path > SEG_GN_BWD_COOP) return fail("seg_op_gn_backward: unknown path");
+    const int esz = dtype == DT_F32 ? 4 : 2;
+    GnBwdArgs e{};
+    for (int i = 0; i < 3; ++i) e.dy[i] = i < a->ndy ? a->dy[i] : nullptr;
+    e.ndy = a->ndy; e.r = a->r; e.scale = a->scale; e.shift = a->shift; e.Q = a->Q; e.coef = a->coef; e.dr = a->dr;
+    e.N = a->N; e.C = a->C; e.V = a->V;
+    if (a->r2) { e.r2 = a->r2; e.scale2 = a->scale2; e.shift2 = a->shift2; e.Q2 = a->Q2; e.coef2 = a->coef2; e.dr2 = a->dr2; }
+    if (a->vdl) { e.vdl = a->vdl; e.vw = a->vw; e.vK = a->vK; }
+    e.rep_q = a->rep_q;
+    GnBwdFinArgs f{}, f2{};
+    f.Q = a->Q; f.stats = a->stats; f.gamma = a->gamma; f.mask = a->mask; f.mask_ld = a->mask_ld; f.mean = a->mean; f.rstd = a->rstd;
+    f.dgamma = a->dgamma; f.dbeta = a->dbeta; f.dbias = a->dbias; f.coef = a->coef;
+    f.N = a->N; f.C = a->C; f.V = a->V; f.rep_q = a->rep_q; f.rep_s = a->rep_s;
+    f2 = f;
+    f2.Q = a->Q2; f2.stats = a->stats2; f2.gamma = a->gamma2; f2.mask = a->mask2; f2.mean = a->mean2; f2.rstd = a->rstd2;
+    f2.dgamma = a->dgamma2; f2.dbeta = a->dbeta2; f2.dbias = a->dbias2; f2.coef = a->coef2;
+    hipStream_t st = (hipStream_t)stream;
+    if (a->path == SEG_GN_BWD_COOP) {
+        if (!gn_bwd_coop_eligible(e, esz)) return fail("seg_op_gn_backward: not eligible for the co-operative kernel (1..3 stored sources, one branch, seg_op_gn_coop_plan)");
+        launch_gn_bwd_coop(e, f, dtype, st);
+    } else if (a->path == SEG_GN_BWD_GROUP) {
+        if (a->r2 || a->vdl || a->ndy < 1) return fail("seg_op_gn_backward: the one-workgroup-per-group form takes 1..3 stored sources and one branch");
+        if (!gn_bwd_group_eligible(a->C, a->V, esz)) return fail("seg_op_gn_backward: shape not eligible for the one-workgroup-per-group form (C >= 64, <= 128 KB per sample)");
+        launch_gn_bwd_group(e, f, dtype, st);
+    } else {
+        if (a->path == SEG_GN_BWD_SEPARATE && (!a->coef || (a->r2 && !a->coef2))) return fail("seg_op_gn_backward: null pointer (coef)");
+        launch_gn_bwd_reduce(e, dtype, st);
+        if (a->path == SEG_GN_BWD_SEPARATE) {
+            if (a->r2) launch_gn_bwd_finalize(f, st, &f2);
+            else launch_gn_bwd_finalize(f, st);
+            launch_gn_bwd_apply(e, dtype, st);
+        } else launch_gn_bwd_apply(e, dtype, st, &f, a->r2 ? &f2 : nullptr);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_gn_backward: launch failed");
+}
+
+int seg_op_gn_coop_plan(int c, long long v, int n, int esz, int* S, int* ku) {
+    if (c < 8) return 0;
+    return gn_bwd_coop_plan(c, v, n, esz, S, ku) ? 1 : 0;
+}
+int seg_op_gn_group_eligible(int c, long long v, int esz) { return gn_bwd_group_eligible(c, v, esz) ? 1 : 0; }
+
+int seg_op_maxpool(const void* in, void* out, const void* dout, void* din, int n, int d, int h, int w, int c, int pd, int ph, int pw, int backward,
+                   int dtype, void* stream) {
+    if (!in || (backward ? (!dout || !din) : !out)) return fail("seg_op_maxpool: null pointer");
+    if (dtype < DT_F32 || dtype > DT_BF16) return fail("seg_op_maxpool: unknown dtype");
+    if (n < 1 || d < 1 || h < 1 || w < 1 || c < 8 || c % 8) return fail("seg_op_maxpool: extents must be positive and C a multiple of 8");
+    if (pd < 1 || pd > 2 || ph < 1 || ph > 2 || pw < 1 || pw > 2 || d % pd || h % ph || w % pw) return fail("seg_op_maxpool: windows are 1 or 2 and divide their extents");
+    PoolArgs a{};
+    a.in = in; a.out = out; a.dout = dout; a.din = din; a.N = n; a.D = d; a.H = h; a.W = w; a.C = c; a.pd = pd; a.ph = ph; a.pw = pw;
+    if (backward) launch_maxpool_bwd(a, dtype, (hipStream_t)stream);
+    else launch_maxpool_fwd(a, dtype, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_maxpool: launch failed");
 }
 
 #define SEG_OK(what) (hipGetLastError() == hipSuccess ? 0 : fail(what ": launch failed"))

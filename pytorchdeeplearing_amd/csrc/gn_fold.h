@@ -45,13 +45,13 @@ __device__ __forceinline__ void gn_fold_block(const GnFinArgs& f, int n, bool pu
         const double mean = s / cnt;
         double var = ss / cnt - mean * mean;
         if (var < 0.0) var = 0.0;
-        const float rstd = (float)(1.0 / sqrt(var + (double)f.eps));
-        const float sc = mk * ga * rstd, sh = mk * (be - ga * (float)mean * rstd);
+        const double rstd = 1.0 / sqrt(var + (double)f.eps);
+        const float sc = (float)((double)mk * ga * rstd), sh = (float)((double)mk * ((double)be - (double)ga * mean * rstd));       // fp64, rounded once (see gn_finalize_kernel)
         sc_s[c] = sc; sh_s[c] = sh;
         if (publish) {
             f.scale[(long long)n * C + c] = sc;
             f.shift[(long long)n * C + c] = sh;
-            if (c % cpg == 0) { f.mean[n * GN_GROUPS + c / cpg] = (float)mean; f.rstd[n * GN_GROUPS + c / cpg] = rstd; }
+            if (c % cpg == 0) { f.mean[n * GN_GROUPS + c / cpg] = (float)mean; f.rstd[n * GN_GROUPS + c / cpg] = (float)rstd; }
         }
     }
     __syncthreads();

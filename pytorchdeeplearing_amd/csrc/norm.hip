@@ -45,17 +45,19 @@ __global__ __launch_bounds__(64) void gn_finalize_kernel(GnFinArgs a0, GnFinArgs
     const double mean = ts / cnt;
     double var = tss / cnt - mean * mean;
     if (var < 0.0) var = 0.0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)a.eps));
+    const double rstd = 1.0 / sqrt(var + (double)a.eps);
     (void)csum;
     if (tid == 0) {
         a.mean[n * GN_GROUPS + g] = (float)mean;
-        a.rstd[n * GN_GROUPS + g] = rstd;
+        a.rstd[n * GN_GROUPS + g] = (float)rstd;
     }
     if (tid < cpg) {
-        const float mk = a.mask ? a.mask[(long long)n * a.mask_ld + c] : 1.f;
-        const float ga = a.gamma[c], be = a.beta[c];
-        a.scale[(long long)n * a.C + c] = mk * ga * rstd;
-        a.shift[(long long)n * a.C + c] = mk * (be - ga * (float)mean * rstd);
+        // in fp64, rounded once: beta - gamma * mean * rstd cancels where a channel's output is centred near zero, and in fp32 the shift
+        // then carries the rounding of its (much larger) terms into every activation of the channel
+        const double mk = a.mask ? (double)a.mask[(long long)n * a.mask_ld + c] : 1.0;
+        const double ga = a.gamma[c], be = a.beta[c];
+        a.scale[(long long)n * a.C + c] = (float)(mk * ga * rstd);
+        a.shift[(long long)n * a.C + c] = (float)(mk * (be - ga * mean * rstd));
     }
 }
 
@@ -678,12 +680,12 @@ __global__ __launch_bounds__(1024) void gn_fwd_group_kernel(GnFwdGroupArgs a) {
         const double mean = ts / cnt;
         double var = tss / cnt - mean * mean;
         if (var < 0.0) var = 0.0;
-        const float rstd = (float)(1.0 / sqrt(var + (double)a.f.eps));
-        if (lane == 0) { a.f.mean[n * GN_GROUPS + g] = (float)mean; a.f.rstd[n * GN_GROUPS + g] = rstd; }
+        const double rstd = 1.0 / sqrt(var + (double)a.f.eps);
+        if (lane == 0) { a.f.mean[n * GN_GROUPS + g] = (float)mean; a.f.rstd[n * GN_GROUPS + g] = (float)rstd; }
         if (lane < cpg) {
-            const float mk = a.f.mask ? a.f.mask[(long long)n * a.f.mask_ld + c] : 1.f;
-            const float ga = a.f.gamma[c], be = a.f.beta[c];
-            const float sc = mk * ga * rstd, sh = mk * (be - ga * (float)mean * rstd);
+            const double mk = a.f.mask ? (double)a.f.mask[(long long)n * a.f.mask_ld + c] : 1.0;
+            const double ga = a.f.gamma[c], be = a.f.beta[c];
+            const float sc = (float)(mk * ga * rstd), sh = (float)(mk * (be - ga * mean * rstd));       // fp64, rounded once (see gn_finalize_kernel)
             ssc[lane] = sc; ssh[lane] = sh;
             a.f.scale[(long long)n * C + c] = sc;
             a.f.shift[(long long)n * C + c] = sh;
@@ -829,9 +831,10 @@ __global__ __launch_bounds__(256, 2) void gn_bwd_coop_kernel(GnBwdCoopArgs a) { 
         }
         __syncthreads();
         if (tid < cpg) {
-            float s1 = 0.f, s2 = 0.f;
+            double d1 = 0.0, d2 = 0.0;                      // (fp64 like gn_bwd_group_kernel: sixteen fp32 additions in a row cost B and Cc a few ulp)
 #pragma unroll
-            for (int w = 0; w < 16; ++w) { s1 += wsum[w][tid >> 3][tid & 7]; s2 += wsum[w][tid >> 3][8 + (tid & 7)]; }
+            for (int w = 0; w < 16; ++w) { d1 += wsum[w][tid >> 3][tid & 7]; d2 += wsum[w][tid >> 3][8 + (tid & 7)]; }
+            const float s1 = (float)d1, s2 = (float)d2;
             unsigned long long w = ((unsigned long long)__builtin_bit_cast(unsigned, s2) << 32) | (unsigned long long)__builtin_bit_cast(unsigned, s1);
             if (w == 0ull) w = 0x80000000ull;                 // "there": +0.0 travels as -0.0
             xwg_store(slot + sl * cpg + tid, w);

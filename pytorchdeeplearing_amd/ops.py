@@ -54,7 +54,40 @@ class StemxArgs(C.Structure):
                 ("N", C.c_int), ("D", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cimg", C.c_int)]
 
 
+class GnFwdArgs(C.Structure):
+    """seg_gn_fwd_args of include/segengine.h"""
+    _fields_ = [("r1", C.c_void_p), ("r2", C.c_void_p), ("res", C.c_void_p), ("out", C.c_void_p),
+                ("stats1", C.c_void_p), ("stats2", C.c_void_p),
+                ("gamma1", C.c_void_p), ("beta1", C.c_void_p), ("gamma2", C.c_void_p), ("beta2", C.c_void_p),
+                ("mask1", C.c_void_p), ("mask2", C.c_void_p), ("mask_ld", C.c_int),
+                ("scale1", C.c_void_p), ("shift1", C.c_void_p), ("mean1", C.c_void_p), ("rstd1", C.c_void_p),
+                ("scale2", C.c_void_p), ("shift2", C.c_void_p), ("mean2", C.c_void_p), ("rstd2", C.c_void_p),
+                ("N", C.c_int), ("C", C.c_int), ("V", C.c_longlong),
+                ("eps", C.c_float), ("rep", C.c_int), ("path", C.c_int)]
+
+
+class GnBwdArgs(C.Structure):
+    """seg_gn_bwd_args of include/segengine.h"""
+    _fields_ = [("dy", C.c_void_p * 3), ("ndy", C.c_int),
+                ("vdl", C.c_void_p), ("vw", C.c_void_p), ("vK", C.c_int),
+                ("r", C.c_void_p), ("r2", C.c_void_p),
+                ("scale", C.c_void_p), ("shift", C.c_void_p), ("scale2", C.c_void_p), ("shift2", C.c_void_p),
+                ("mean", C.c_void_p), ("rstd", C.c_void_p), ("mean2", C.c_void_p), ("rstd2", C.c_void_p),
+                ("stats", C.c_void_p), ("stats2", C.c_void_p),
+                ("gamma", C.c_void_p), ("gamma2", C.c_void_p),
+                ("mask", C.c_void_p), ("mask2", C.c_void_p), ("mask_ld", C.c_int),
+                ("Q", C.c_void_p), ("Q2", C.c_void_p),
+                ("coef", C.c_void_p), ("coef2", C.c_void_p),
+                ("dr", C.c_void_p), ("dr2", C.c_void_p),
+                ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("dbias", C.c_void_p),
+                ("dgamma2", C.c_void_p), ("dbeta2", C.c_void_p), ("dbias2", C.c_void_p),
+                ("N", C.c_int), ("C", C.c_int), ("V", C.c_longlong),
+                ("rep_q", C.c_int), ("rep_s", C.c_int), ("path", C.c_int)]
+
+
 def check_abi(lib):
+    assert lib.dll.seg_abi_sizeof(5) == C.sizeof(GnFwdArgs), (lib.dll.seg_abi_sizeof(5), C.sizeof(GnFwdArgs))
+    assert lib.dll.seg_abi_sizeof(6) == C.sizeof(GnBwdArgs), (lib.dll.seg_abi_sizeof(6), C.sizeof(GnBwdArgs))
     assert lib.dll.seg_abi_sizeof(3) == C.sizeof(StemxArgs), (lib.dll.seg_abi_sizeof(3), C.sizeof(StemxArgs))
     assert lib.dll.seg_abi_sizeof(0) == C.sizeof(ConvArgs), (lib.dll.seg_abi_sizeof(0), C.sizeof(ConvArgs))
     assert lib.dll.seg_abi_sizeof(1) == C.sizeof(WgradArgs)
@@ -359,3 +392,104 @@ def stemx(mode, img, w3p, dtype, ndim, w1p=None, bias3=None, bias1=None, scale=N
     lib.check(lib.seg_op_stemx(C.byref(a), mode, ndim, _capi.DTYPE[dtype], dw3.data_ptr() if dw3 is not None else None,
                                dw1.data_ptr() if (dw1 is not None and two) else None, _capi.stream_for(dev)), "seg_op_stemx")
     return res()
+
+
+GN_FWD_PATH = {"finalize": 0, "fold": 1, "group": 2}
+GN_BWD_PATH = {"separate": 0, "fold": 1, "group": 2, "coop": 3}
+_ESZ = {"f32": 4, "f16": 2, "bf16": 2}
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def gn_coop_plan(C_, V, N, dtype):
+    """(S, ku) of the co-operative GroupNorm-backward kernel for the shape, or None where it is not eligible"""
+    S, ku = C.c_int(0), C.c_int(0)
+    ok = _capi.host_library().seg_op_gn_coop_plan(C_, V, N, _ESZ[dtype], C.byref(S), C.byref(ku))
+    return (S.value, ku.value) if ok else None
+
+
+def gn_group_eligible(C_, V, dtype):
+    return bool(_capi.host_library().seg_op_gn_group_eligible(C_, V, _ESZ[dtype]))
+
+
+def gn_forward(r1, stats1, gamma1, beta1, dtype, path, rep, mask1=None, r2=None, stats2=None, gamma2=None, beta2=None, mask2=None, res=None,
+               eps=1e-5, bufs=None):
+    """GroupNorm(8) + dropout multiplier + ReLU (+ second branch + residual) of r1 [N, V, C] through the named path ("finalize" | "fold" | "group").
+    stats [32, N, C, 2] fp64 with `rep` replicas in use; mask [N, ld] fp32.  Returns a dict: out, scale1, shift1, mean1, rstd1 (and ...2 with r2).
+    bufs: output tensors to use instead of fresh ones (same keys)."""
+    lib = _capi.lib_for(r1.device)
+    N, V, C_ = r1.shape
+    o = dict(bufs or {})
+    o.setdefault("out", _alloc((N, V, C_), TORCH_DTYPE[dtype], r1.device, zero=True))
+    for b in ("1", "2") if r2 is not None else ("1",):
+        for k, shp in (("scale", (N, C_)), ("shift", (N, C_)), ("mean", (N, 8)), ("rstd", (N, 8))):
+            o.setdefault(k + b, _alloc(shp, torch.float32, r1.device, zero=True))
+    a = GnFwdArgs()
+    a.r1, a.r2, a.res, a.out = _ptr(r1), _ptr(r2), _ptr(res), _ptr(o["out"])
+    a.stats1, a.stats2 = _ptr(stats1), _ptr(stats2)
+    a.gamma1, a.beta1, a.gamma2, a.beta2 = _ptr(gamma1), _ptr(beta1), _ptr(gamma2), _ptr(beta2)
+    a.mask1, a.mask2 = _ptr(mask1), _ptr(mask2)
+    m = mask1 if mask1 is not None else mask2
+    a.mask_ld = m.shape[1] if m is not None else 0
+    for k in ("scale", "shift", "mean", "rstd"):
+        setattr(a, k + "1", _ptr(o[k + "1"]))
+        setattr(a, k + "2", _ptr(o.get(k + "2")))
+    a.N, a.C, a.V, a.eps, a.rep, a.path = N, C_, V, eps, rep, GN_FWD_PATH.get(path, path)
+    lib.check(lib.seg_op_gn_forward(C.byref(a), _capi.DTYPE[dtype], _capi.stream_for(r1.device)), "seg_op_gn_forward")
+    return o
+
+
+def gn_backward(dys, r, fwd, stats, gamma, dtype, path, rep_q, rep_s, mask=None, vdl=None, vw=None, second=None, bufs=None):
+    """Backward of gn_forward through the named path ("separate" | "fold" | "group" | "coop").  dys: list of 0..3 gradient tensors [N, V, C];
+    vdl [N, K, V] / vw [K, C] fp32: the virtual head source; fwd: dict scale / shift / mean / rstd as the forward wrote them; second: dict
+    r, scale, shift, mean, rstd, stats, gamma, mask of a second branch fed by the same sources.  Returns a dict: Q [32, N, C, 2], coef, dr, dgamma, dbeta,
+    dbias (and ...2).  bufs: output tensors to use instead of fresh zeroed ones (same keys)."""
+    lib = _capi.lib_for(r.device)
+    N, V, C_ = r.shape
+    o = dict(bufs or {})
+    for b in ("", "2") if second is not None else ("",):
+        o.setdefault("Q" + b, _alloc((32, N, C_, 2), torch.float64, r.device, zero=True))
+        o.setdefault("coef" + b, _alloc((N, C_, 3), torch.float32, r.device, zero=True))
+        o.setdefault("dr" + b, _alloc((N, V, C_), TORCH_DTYPE[dtype], r.device, zero=True))
+        for k in ("dgamma", "dbeta", "dbias"):
+            o.setdefault(k + b, _alloc((C_,), torch.float32, r.device, zero=True))
+    a = GnBwdArgs()
+    for i, d in enumerate(dys):
+        a.dy[i] = _ptr(d)
+    a.ndy = len(dys)
+    if vdl is not None:
+        a.vdl, a.vw, a.vK = _ptr(vdl), _ptr(vw), vdl.shape[1]
+    a.r, a.stats, a.gamma, a.mask = _ptr(r), _ptr(stats), _ptr(gamma), _ptr(mask)
+    for k in ("scale", "shift", "mean", "rstd"):
+        setattr(a, k, _ptr(fwd[k]))
+    m = mask
+    if second is not None:
+        a.r2, a.stats2, a.gamma2, a.mask2 = _ptr(second["r"]), _ptr(second["stats"]), _ptr(second["gamma"]), _ptr(second.get("mask"))
+        for k in ("scale", "shift", "mean", "rstd"):
+            setattr(a, k + "2", _ptr(second[k]))
+        m = m if m is not None else second.get("mask")
+    a.mask_ld = m.shape[1] if m is not None else 0
+    for k in ("Q", "coef", "dr", "dgamma", "dbeta", "dbias"):
+        setattr(a, k, _ptr(o[k]))
+        setattr(a, k + "2", _ptr(o.get(k + "2")))
+    a.N, a.C, a.V, a.rep_q, a.rep_s, a.path = N, C_, V, rep_q, rep_s, GN_BWD_PATH.get(path, path)
+    lib.check(lib.seg_op_gn_backward(C.byref(a), _capi.DTYPE[dtype], _capi.stream_for(r.device)), "seg_op_gn_backward")
+    return o
+
+
+def maxpool(x, window, dtype, dout=None):
+    """max-pool of x [N, D, H, W, C] with window = stride (pd, ph, pw); with dout (coarse): the gradient at x instead (first maximum in scan order)"""
+    lib = _capi.lib_for(x.device)
+    N, D, H, W, C_ = x.shape
+    pd, ph, pw = window
+    if dout is None:
+        out = _alloc((N, D // pd, H // ph, W // pw, C_), TORCH_DTYPE[dtype], x.device, zero=True)
+        lib.check(lib.seg_op_maxpool(x.data_ptr(), out.data_ptr(), None, None, N, D, H, W, C_, pd, ph, pw, 0, _capi.DTYPE[dtype],
+                                     _capi.stream_for(x.device)), "seg_op_maxpool")
+        return out
+    din = _alloc((N, D, H, W, C_), TORCH_DTYPE[dtype], x.device, zero=True)
+    lib.check(lib.seg_op_maxpool(x.data_ptr(), None, dout.data_ptr(), din.data_ptr(), N, D, H, W, C_, pd, ph, pw, 1, _capi.DTYPE[dtype],
+                                 _capi.stream_for(x.device)), "seg_op_maxpool")
+    return din

@@ -326,31 +326,6 @@ def test_conv3_halo_exact(dev, dtype, case):
 
 @pytest.mark.parametrize("dtype", DT)
 @pytest.mark.parametrize("case", HALO_CASES)
-def test_conv3_halo_exact(dev, dtype, case):
-    ndim, N, sp, cin, cout = case
-    g = torch.Generator().manual_seed(sum(sp) + cin)
-    x = ints((N, cin) + sp, -2, 2, g)
-    w = ints((cout, cin) + (3,) * ndim, -1, 1, g, density=0.15)
-    b = ints((cout,), -3, 3, g)
-    conv = F.conv3d if ndim == 3 else F.conv2d
-    xr = x.clone().requires_grad_(True)
-    ref = conv(xr, w, b, padding=1)
-    assert float(ref.abs().max()) <= 256
-    out, stats = ops.conv3(to_dev(cl(x), dtype, dev), ops.pack(w.to(dev), "conv_fwd", dtype), dtype, ndim, cout,
-                           bias=ops.aligned_like(b.to(dev)), want_stats=True)
-    assert torch.equal(ncdhw(out.float().cpu(), ndim), ref.detach())
-    rs = torch.stack([ref.detach().double().flatten(2).sum(2), (ref.detach().double() ** 2).flatten(2).sum(2)], dim=2)
-    assert torch.equal(stats.cpu(), rs)
-    # data-gradient through the same kernel with the flipped layout
-    dy = ints(tuple(ref.shape), -1, 1, g, density=0.4)
-    ref.backward(dy)
-    assert float(xr.grad.abs().max()) <= 256
-    got = ops.conv3(to_dev(cl(dy), dtype, dev), ops.pack(w.to(dev), "conv_dgrad", dtype), dtype, ndim, cin)
-    assert torch.equal(ncdhw(got.float().cpu(), ndim), xr.grad)
-
-
-@pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("case", HALO_CASES)
 def test_wgrad3_halo_exact(dev, dtype, case):
     ndim, N, sp, cin, cout = case
     g = torch.Generator().manual_seed(sum(sp) + cout)
