@@ -45,7 +45,7 @@ extern "C" {
 
 typedef struct seg_engine* seg_handle;
 
-enum { SEG_NET_VNET = 0, SEG_NET_UNET = 1 };
+enum { SEG_NET_VNET = 0, SEG_NET_UNET = 1, SEG_NET_RESNET = 2 };
 enum { SEG_F32 = 0, SEG_F16 = 1, SEG_BF16 = 2 };
 enum { SEG_LABEL_U8 = 0, SEG_LABEL_I32 = 1, SEG_LABEL_I64 = 2, SEG_LABEL_F32 = 3,
        /* flag, or-ed into a label type: every kernel reads the label as (value != 0): `y[y != 0] = 1` of the binary training loops
@@ -78,7 +78,17 @@ enum { SEG_MASKS_EVAL = 0, SEG_MASKS_GIVEN = 1, SEG_MASKS_RANDOM = 2 };
 /* networks/VNet3d.py:109 VNet3d(image_channel, numclass, init_features=16), networks/VNet2d.py:109,
  * networks/Unet3d.py:11 UNet3d(in_channels, out_channels, init_features=16), networks/Unet2d.py:11.
  * ndim = 2 or 3.  in_channels 1..16 (1 in 3-D / 1..3 in 2-D take the fused image stem; more channels are zero-padded to a 16-channel image tensor
- * and run through the ordinary 16-channel convs), num_class 1..16, init_features 16. */
+ * and run through the ordinary 16-channel convs), num_class 1..16, init_features 16.
+ *
+ * SEG_NET_RESNET: the classifiers networks/ResNet3d.py:72-118 / ResNet2d.py ResNet3d(image_channel, numclass) - the VNet encoder (in_tr, down_tr32 ..
+ * down_tr256), global average pooling, Linear(256, 128) + ReLU + Linear(128, numclass).  70 parameter tensors in state_dict order, the last four
+ * fc_layers.0.weight [128][256], fc_layers.0.bias, fc_layers.2.weight [numclass][128], fc_layers.2.bias.  Channel dropout sits only behind each down_conv
+ * (4 calls of 32, 64, 128, 256 channels; the input block and the LUConvs have none and take multiplier 1 in every mask mode).  The reference reads an
+ * undefined module global `prob` for the dropout probability and cannot be constructed as shipped; p = 0.2, the VNet value, is used.
+ * For this kind `logits` / `probs` / `dlogits` are [N][num_class] fp32 (the planar layout with one voxel): probs = sigmoid for num_class == 1, soft-max
+ * over the classes otherwise.  seg_forward, seg_backward*, seg_train_step and the captured step work as for the other kinds; the losses of
+ * seg_train_step are evaluated with v = 1 (SEG_LOSS_BINARY_CE, BINARY_FOCAL, MULTI_CE, MULTI_FOCAL are the reference's choices), and out3[1..2]
+ * (dice / iou of a one-voxel "mask") are written but carry no meaning. */
 int seg_create(int net_kind, int ndim, int in_channels, int num_class, int init_features, int dtype,
                seg_handle* out);
 void seg_destroy(seg_handle h);
@@ -90,7 +100,7 @@ int seg_param_info(seg_handle h, int index, char* name, int name_cap, int* shape
                    long long* offset);
 long long seg_param_numel(seg_handle h);
 
-/* Number of channel-dropout calls per forward (34 VNet / 18 UNet) and the row stride of the
+/* Number of channel-dropout calls per forward (34 VNet / 18 UNet / 4 ResNet) and the row stride of the
  * multiplier table [calls][N][ld] used by SEG_MASKS_GIVEN (networks/VNet3d.py:11,31,51,67). */
 int seg_dropout_calls(seg_handle h);
 int seg_dropout_ld(seg_handle h);
@@ -486,6 +496,20 @@ int seg_op_gn_group_eligible(int c, long long v, int esz);
  * backward = 1: din (fine) = dout (coarse) routed to the first maximum of each window of `in` in (d, h, w) scan order, zero elsewhere. */
 int seg_op_maxpool(const void* in, void* out, const void* dout, void* din, int n, int d, int h, int w, int c, int pd, int ph, int pw,
                    int backward, int dtype, void* stream);
+/* Classification head of SEG_NET_RESNET (networks/ResNet3d.py:61-69,91-96,114-116) on the channels-last activation act [N][V][256] (run dtype):
+ *   pooled[n][k] = mean_v act[n][v][k]        h = relu(W1 pooled + b1), W1 [128][256]        logits = W2 h + b2, W2 [C][128]        probs = sigmoid (C == 1) / soft-max
+ * forward leaves pooled (N x 256) and h (N x 128), fp32, in `ws` (seg_op_cls_head_ws_bytes(n, v) bytes, 256-byte aligned) for the backward call, which
+ * takes dlogits [N][C] (times the loss scale) and gives dW2 = dl^T h, db2, dh = (W2^T dl) [h > 0], dW1 = dh^T pooled, db1 and
+ * dact[n][v][k] = (W1^T dh)[n][k] / V in the run dtype.  zero_grads = 0: the parameter gradients are ADDED to what the four buffers hold; 1: they replace it.
+ * Nothing is read back, no grid depends on data and there are no floating-point atomics: the voxel sum is an fp64 sum per 64-voxel slab (ascending voxels)
+ * folded over the slabs in ascending order, the FC dot products are fp32 fmaf chains in a fixed lane order, every sum over samples runs over ascending n -
+ * two calls agree bit for bit.  n >= 1, 1 <= v < 2^31 / 256, 1 <= c <= 16.  seg_op_cls_head_ws_offset: the byte offset of pooled / h inside `ws`. */
+long long seg_op_cls_head_ws_bytes(int n, long long v);
+long long seg_op_cls_head_ws_offset(int n, long long v, int what /* 0: pooled, 1: h */);
+int seg_op_cls_head_forward(const void* act, const float* w1, const float* b1, const float* w2, const float* b2, float* logits, float* probs, int n,
+                            long long v, int c, void* ws, int dtype, void* stream);
+int seg_op_cls_head_backward(const float* dlogits, const float* w1, const float* w2, float* dw1, float* db1, float* dw2, float* db2, void* dact, int n,
+                             long long v, int c, int zero_grads, void* ws, int dtype, void* stream);
 
 /* ---- soft-clDice building blocks (model/lossescldice.py:5-59; corrected restatement).
  * Planar fp32 tensors [planes][D][H][W]; nd = 3 pools 3x3x3 over (D,H,W), nd = 2 pools 3x3 over (H,W); stride 1, pad 1,
@@ -623,7 +647,8 @@ enum {
     SEG_K_CONV3_SB = 9,       /* every other halo-tile conv (16-channel top level, deep levels) */
     SEG_K_GN_GROUP = 10,      /* one-launch GroupNorm passes of the small tensors (forward and backward) */
     SEG_K_MISC = 11,          /* everything else of a train step: fill + ingest, loss reduce / finalize / backward, fused optimiser, weight re-pack */
-    SEG_K_COUNT = 12
+    SEG_K_CLS_HEAD = 12,      /* classification head (SEG_NET_RESNET): pooling, the two FC layers, their backward */
+    SEG_K_COUNT = 13
 };
 int seg_profile_enable(seg_handle h, unsigned mask);
 int seg_profile_read(seg_handle h, int* calls, float* ms, double* bytes, double* flops);

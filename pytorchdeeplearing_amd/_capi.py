@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # SEGENGINE_LIB: tuning builds only (tools/build_variant.py); the product library is lib/libsegengine.so
 LIB_PATH = os.environ.get("SEGENGINE_LIB") or os.path.join(HERE, "lib", "libsegengine.so")
 
-NET_KIND = {"vnet": 0, "unet": 1}
+NET_KIND = {"vnet": 0, "unet": 1, "resnet": 2}
 DTYPE = {"f32": 0, "fp32": 0, "float32": 0, "f16": 1, "fp16": 1, "float16": 1, "bf16": 2, "bfloat16": 2}
 LABEL_TYPES = {"torch.uint8": 0, "torch.int32": 1, "torch.int64": 2, "torch.float32": 3}
 LOSS_KIND = {
@@ -26,7 +26,7 @@ MASKS_EVAL, MASKS_GIVEN, MASKS_RANDOM = 0, 1, 2
 def label_type(t, binarize=False):
     """C-ABI label type of a target tensor (+ the device-side binarise flag)"""
     return LABEL_TYPES[str(t.dtype)] | (LABEL_BINARIZE if binarize else 0)
-KERNEL_CLASSES = ["conv3", "wgrad3", "conv_generic", "wgrad_generic", "stem", "gn_act", "gn_bwd_reduce", "gn_bwd_apply", "head", "conv3_smallbox", "gn_group", "misc"]
+KERNEL_CLASSES = ["conv3", "wgrad3", "conv_generic", "wgrad_generic", "stem", "gn_act", "gn_bwd_reduce", "gn_bwd_apply", "head", "conv3_smallbox", "gn_group", "misc", "cls_head"]
 
 _vp, _i, _ll, _f, _d = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_double
 
@@ -96,6 +96,10 @@ SIGNATURES = {
     "seg_op_gn_coop_plan": (_i, [_i, _ll, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "seg_op_gn_group_eligible": (_i, [_i, _ll, _i]),
     "seg_op_maxpool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "seg_op_cls_head_ws_bytes": (_ll, [_i, _ll]),
+    "seg_op_cls_head_ws_offset": (_ll, [_i, _ll, _i]),
+    "seg_op_cls_head_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _vp, _i, _vp]),
+    "seg_op_cls_head_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _i, _vp, _i, _vp]),
     "seg_op_pool3": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "seg_op_skel_iter": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "seg_op_skel_iter_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

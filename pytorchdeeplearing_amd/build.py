@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libsegengine.so")
-SRCS = ["conv.hip", "conv3.hip", "conv3x.hip", "conv3x_f16_3d.hip", "conv3x_f16_2d.hip", "conv3x_bf16_3d.hip", "conv3x_bf16_2d.hip", "wgrad.hip", "stemx.hip", "norm.hip", "misc.hip", "lovasz.hip", "ssim.hip", "cldice.hip", "surface.hip", "augment.hip", "postproc.hip", "prepost.hip", "engine.hip", "engine_plan.hip", "capi_ops.hip"]
+SRCS = ["conv.hip", "conv3.hip", "conv3x.hip", "conv3x_f16_3d.hip", "conv3x_f16_2d.hip", "conv3x_bf16_3d.hip", "conv3x_bf16_2d.hip", "wgrad.hip", "stemx.hip", "norm.hip", "misc.hip", "cls_head.hip", "lovasz.hip", "ssim.hip", "cldice.hip", "surface.hip", "augment.hip", "postproc.hip", "prepost.hip", "engine.hip", "engine_plan.hip", "capi_ops.hip"]
 ID_UNIT = "engine.hip"          # compiled with -DSEG_BUILD_ID
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -munsafe-fp-atomics: fp32 / fp64 atomicAdd as the hardware instruction instead of a compare-and-swap loop (every buffer the library adds into is ordinary

@@ -543,6 +543,39 @@ int seg_op_maxpool(const void* in, void* out, const void* dout, void* din, int n
     return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_maxpool: launch failed");
 }
 
+static int cls_head_extents_ok(int n, long long v, int c) { return n >= 1 && n <= 65535 && v >= 1 && v < (1ll << 31) / CLS_K && c >= 1 && c <= 16; }
+long long seg_op_cls_head_ws_bytes(int n, long long v) {
+    if (!cls_head_extents_ok(n, v, 1)) return fail("seg_op_cls_head_ws_bytes: n must be 1..65535 and v in [1, 2^31 / 256)");
+    return (long long)cls_head_ws_bytes(n, v);
+}
+long long seg_op_cls_head_ws_offset(int n, long long v, int what) {
+    if (!cls_head_extents_ok(n, v, 1) || what < 0 || what > 1) return fail("seg_op_cls_head_ws_offset: bad extents, or `what` not 0 (pooled) / 1 (h)");
+    return (long long)cls_head_ws_offset(n, v, what);
+}
+int seg_op_cls_head_forward(const void* act, const float* w1, const float* b1, const float* w2, const float* b2, float* logits, float* probs, int n,
+                            long long v, int c, void* ws, int dtype, void* stream) {
+    if (!act || !w1 || !b1 || !w2 || !b2 || !logits || !probs || !ws) return fail("seg_op_cls_head_forward: null pointer");
+    if (dtype < DT_F32 || dtype > DT_BF16) return fail("seg_op_cls_head_forward: unknown dtype");
+    if (!cls_head_extents_ok(n, v, c)) return fail("seg_op_cls_head_forward: n must be 1..65535, v in [1, 2^31 / 256), c 1..16");
+    if ((uintptr_t)ws & 255) return fail("seg_op_cls_head_forward: the workspace must be 256-byte aligned");
+    ClsHeadArgs a{};
+    a.act = act; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.logits = logits; a.probs = probs; a.N = n; a.V = v; a.C = c; a.ws = (char*)ws;
+    launch_cls_head_fwd(a, dtype, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_cls_head_forward: launch failed");
+}
+int seg_op_cls_head_backward(const float* dlogits, const float* w1, const float* w2, float* dw1, float* db1, float* dw2, float* db2, void* dact, int n,
+                             long long v, int c, int zero_grads, void* ws, int dtype, void* stream) {
+    if (!dlogits || !w1 || !w2 || !dw1 || !db1 || !dw2 || !db2 || !dact || !ws) return fail("seg_op_cls_head_backward: null pointer");
+    if (dtype < DT_F32 || dtype > DT_BF16) return fail("seg_op_cls_head_backward: unknown dtype");
+    if (!cls_head_extents_ok(n, v, c)) return fail("seg_op_cls_head_backward: n must be 1..65535, v in [1, 2^31 / 256), c 1..16");
+    if ((uintptr_t)ws & 255) return fail("seg_op_cls_head_backward: the workspace must be 256-byte aligned");
+    ClsHeadArgs a{};
+    a.dlogits = dlogits; a.w1 = w1; a.w2 = w2; a.dw1 = dw1; a.db1 = db1; a.dw2 = dw2; a.db2 = db2; a.dact = dact; a.accumulate = zero_grads ? 0 : 1;
+    a.N = n; a.V = v; a.C = c; a.ws = (char*)ws;
+    launch_cls_head_bwd(a, dtype, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_cls_head_backward: launch failed");
+}
+
 #define SEG_OK(what) (hipGetLastError() == hipSuccess ? 0 : fail(what ": launch failed"))
 int seg_op_pool3(const float* x, float* out, int planes, int d, int h, int w, int nd, int is_min, void* stream) {
     if (!x || !out || (nd != 2 && nd != 3)) return fail("seg_op_pool3: bad arguments");

@@ -17,7 +17,7 @@ extern "C" {
 
 int seg_create(int net_kind, int ndim, int in_channels, int num_class, int init_features, int dtype, seg_handle* out) {
     if (!out) return fail("seg_create: out is null");
-    if (net_kind != SEG_NET_VNET && net_kind != SEG_NET_UNET) return fail("seg_create: unknown net kind");
+    if (net_kind != SEG_NET_VNET && net_kind != SEG_NET_UNET && net_kind != SEG_NET_RESNET) return fail("seg_create: unknown net kind");
     if (ndim != 2 && ndim != 3) return fail("seg_create: ndim must be 2 or 3");
     if (dtype < 0 || dtype > 2) return fail("seg_create: dtype must be SEG_F32/F16/BF16");
     if (init_features != 16) return fail("seg_create: init_features must be 16 (GroupNorm(8) tiles; the reference never overrides the default)");
@@ -267,7 +267,7 @@ int seg_train_step(seg_handle h, const seg_train_args* a, void* stream) {
     // Serial section at the step boundary (profiles/r04_trace_timeline.txt: fill, overflow check, Adam, counter, re-pack, masks, counter, fill,
     // ingest - nothing overlaps them): the one-wave bookkeeping launches ride on their neighbours.  SEG_STEP_RIDERS=0: separate launches.
     const bool riders = knob_i("SEG_STEP_RIDERS", 1) != 0;
-    const long long v = h->vol(0);
+    const long long v = h->out_vol();
     struct RideGuard { seg_engine* e; ~RideGuard() { e->ride_on = false; e->ride_zero = nullptr; } } ride_guard{h};      // every way out of the step
     h->ride_on = riders; h->head_zeroed = false;
     h->ride_ingest = StepRider{}; h->ride_pack = StepRider{};

@@ -9,10 +9,11 @@
 //   UNIT  raw = conv(in0 [, in1 as virtual concat]) ; optional GroupNorm(8)+dropout+ReLU parameters
 //   ACT   out = relu-gn(unit_a) [+ relu-gn(unit_b)] [+ residual tensor]
 //   POOL  out = maxpool 2^d (UNet)          HEAD  logits/probs
+//   CLS   logits/probs [N][classes] = FC(relu(FC(mean over the voxels of `in`)))   (the ResNet classifiers: encoder + this step, no HEAD, no up path)
 // Backward is derived from the same list in reverse: every tensor collects up to three gradient
 // contributions (residual fan-in, skip connections) that the GroupNorm-backward kernels sum on the
 // fly, so no explicit `add` or `cat` tensor is ever materialised.
-// Reference structure: networks/VNet3d.py:25-158, networks/Unet3d.py:6-86 (+ the 2-D twins).
+// Reference structure: networks/VNet3d.py:25-158, networks/Unet3d.py:6-86, networks/ResNet3d.py:24-118 (+ the 2-D twins).
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -30,7 +31,7 @@ extern thread_local std::string g_err;          // seg_last_error(); defined in 
 int fail(const std::string& m);                  // sets g_err, returns -1
 
 enum ConvKind { CK_K3, CK_K1, CK_K2S2, CK_KT, CK_STEM3, CK_STEM1 };
-enum StepType { ST_UNIT, ST_ACT, ST_POOL, ST_HEAD };
+enum StepType { ST_UNIT, ST_ACT, ST_POOL, ST_HEAD, ST_CLS };
 
 struct Param { std::string name; std::vector<int> shape; long long off; long long numel; };
 
@@ -48,7 +49,7 @@ struct Step {
     int ck = 0, in0 = -1, in1 = -1, raw = -1, Cin = 0, Cout = 0;
     int w = -1, b = -1, gn_w = -1, gn_b = -1;   // param indices (-1: absent)
     int cin_par = 0;                          // input channels of the weight PARAMETER when the conv reads a zero-padded image tensor (0: Cin)
-    int mask_slot = -1;
+    int mask_slot = -1;                       // row of the dropout multiplier table; -1: a GroupNorm unit without dropout (multiplier 1 in every mask mode)
     size_t stats = 0, scale = 0, shift = 0, mean = 0, rstd = 0, Q = 0, coef = 0;
     size_t wp_fwd = 0, wp_dg0 = 0, wp_dg1 = 0;
     bool fused_stem = false;                  // image stem evaluated inside the fused input block of its ACT step (stemx.hip)
@@ -65,8 +66,10 @@ struct Step {
     bool vact = false;       // the output tensor is never written: its only reader applies the activation on load (Planner::plan)
     bool rq_fused = false;   // ACT (vact): the GroupNorm-backward sums of its unit ride on the data-gradient launch of the 1^d conv that reads it (no reduce launch)
     bool head_fused = false; // ACT: this pass also evaluates the 1^d head that reads its output; HEAD: evaluated by that pass (no launch of its own)
-    // POOL / HEAD
+    // POOL / HEAD / CLS
     int in = -1;
+    int w2 = -1, b2 = -1;    // CLS: second FC layer (w / b: the first)
+    size_t cls_ws = 0;       // CLS: pooled / hidden activations and scratch of the head kernels (cls_head_ws_bytes)
 };
 
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
@@ -242,7 +245,8 @@ struct seg_engine {
         ready_used = 0;
         side_used = false;
     }
-    const float* mask_base(int slot) const {          // dropout multipliers of unit `slot`: table [slot][N][ld]
+    const float* mask_base(int slot) const {          // dropout multipliers of unit `slot`: table [slot][N][ld]; null (= 1): eval mode, or a unit without dropout
+        if (mask_mode == SEG_MASKS_EVAL || slot < 0) return nullptr;
         return (const float*)(ws + off_masks) + (size_t)slot * N * ld_mask();
     }
     void run_ops(std::vector<std::function<void(hipStream_t)>>& ops, int b, int e, hipStream_t st) {
@@ -293,11 +297,12 @@ struct seg_engine {
     int dim_h(int l) const { return H >> l; }
     int dim_w(int l) const { return W >> l; }
     long long vol(int l) const { return (long long)dim_d(l) * dim_h(l) * dim_w(l); }
+    long long out_vol() const { return kind == SEG_NET_RESNET ? 1 : vol(0); }      // voxels per sample and class of logits / probs / dlogits
 };
 
 namespace segi {
 int check_handle(seg_handle h);
-void build_network(seg_engine& e, int net_kind);          // engine_plan.hip: the step list of a VNet / UNet (Builder)
+void build_network(seg_engine& e, int net_kind);          // engine_plan.hip: the step list of a VNet / UNet / ResNet (Builder)
 void plan_engine(seg_engine& e);                          // engine_plan.hip: workspace layout + forward / backward schedules for the planned shape (Planner)
 int fill_loss(LossArgs& a, const float* logits, const void* target, int label_type, int n, int c, long long v, int loss_kind, float focal_alpha,
               float focal_gamma, void* ws);               // capi_ops.hip

@@ -47,28 +47,30 @@ struct Builder {
         const int k = conv_geom(ck, nd).k, cpar = cin_par(in0, in1);
         return param(cname + ".weight", ck == CK_KT ? kshape(cpar, Cout, k) : kshape(Cout, cpar, k));
     }
-    // appends the UNIT step of a conv whose parameters exist: w, b (-1: no bias), GroupNorm gw / gb (-1: none)
-    int add_unit(int ck, int w, int b, int in0, int in1, int Cout, int lvl, int gw, int gb) {
+    // appends the UNIT step of a conv whose parameters exist: w, b (-1: no bias), GroupNorm gw / gb (-1: none); drop: channel dropout behind the GroupNorm
+    int add_unit(int ck, int w, int b, int in0, int in1, int Cout, int lvl, int gw, int gb, bool drop = true) {
         Step s; s.type = ST_UNIT; s.ck = ck; s.in0 = in0; s.in1 = in1;
         s.Cin = cin(in0, in1);
         s.Cout = Cout; s.w = w; s.b = b;
         if (e.tens[in0].image && e.pad_img) s.cin_par = e.in_ch;
         if (gw >= 0) {
             s.gn_w = gw; s.gn_b = gb;
-            s.mask_slot = (int)e.drop_ch.size();
-            e.drop_ch.push_back(Cout);
+            if (drop) {
+                s.mask_slot = (int)e.drop_ch.size();
+                e.drop_ch.push_back(Cout);
+            }
         }
         s.raw = tensor(Cout, lvl);
         e.steps.push_back(s);
         return (int)e.steps.size() - 1;
     }
     // conv (+ GroupNorm "<gname>.weight/.bias"; empty gname: none): creates the parameters in the reference's order, then the step
-    int unit(int ck, const std::string& cname, bool bias, int in0, int in1, int Cout, int lvl_out, const std::string& gname) {
+    int unit(int ck, const std::string& cname, bool bias, int in0, int in1, int Cout, int lvl_out, const std::string& gname, bool drop = true) {
         const int w = conv_weight(cname, ck, in0, in1, Cout);
         const int b = bias ? param(cname + ".bias", {Cout}) : -1;
         int gw = -1, gb = -1;
         if (!gname.empty()) { gw = param(gname + ".weight", {Cout}); gb = param(gname + ".bias", {Cout}); }
-        return add_unit(ck, w, b, in0, in1, Cout, lvl_out, gw, gb);
+        return add_unit(ck, w, b, in0, in1, Cout, lvl_out, gw, gb, drop);
     }
     int act(int ua, int ub, int res) {
         Step s; s.type = ST_ACT; s.ua = ua; s.ub = ub; s.res = res;
@@ -90,7 +92,20 @@ struct Builder {
         e.steps.push_back(s);
     }
 
-    void build_vnet() {   // networks/VNet3d.py:102-158
+    // classification head on the activation `in`: fc_layers.0 (Linear(C, 128)), ReLU, fc_layers.2 (Linear(128, classes))
+    void cls_head(int in, const std::string& name) {
+        Step s; s.type = ST_CLS; s.in = in; s.Cin = e.tens[in].C; s.Cout = e.ncls;
+        s.w = param(name + ".0.weight", {CLS_H, s.Cin});
+        s.b = param(name + ".0.bias", {CLS_H});
+        s.w2 = param(name + ".2.weight", {e.ncls, CLS_H});
+        s.b2 = param(name + ".2.bias", {e.ncls});
+        e.steps.push_back(s);
+    }
+
+    // InputTransition + four DownTransitions, shared by the VNet (VNet3d.py:25-59) and the ResNet classifiers (ResNet3d.py:24-58).  Returns the level-4
+    // tensor; `skips` receives the outputs of levels 0 .. 4.  all_drop: channel dropout behind every GroupNorm (VNet); otherwise only behind down_conv
+    // (ResNet: do1 is in place, so the residual `down` is the dropped tensor - drop(relu(.)) == relu(drop(.)) for multipliers >= 0, the VNet unit).
+    int encoder(std::vector<int>& skips, bool all_drop) {
         const int F = e.feat;
         const int x = tensor(e.pad_img ? 16 : e.in_ch, 0, true);
         e.image_ten = x;
@@ -99,10 +114,10 @@ struct Builder {
         const int w3 = conv_weight("in_tr.conv1", ck3, x, -1, F), b3 = param("in_tr.conv1.bias", {F});
         const int w1 = conv_weight("in_tr.conv2", ck1, x, -1, F), b1 = param("in_tr.conv2.bias", {F});
         const int gw = param("in_tr.bn1.weight", {F}), gb = param("in_tr.bn1.bias", {F});
-        const int ua = add_unit(ck3, w3, b3, x, -1, F, 0, gw, gb);
-        const int ub = add_unit(ck1, w1, b1, x, -1, F, 0, gw, gb);
+        const int ua = add_unit(ck3, w3, b3, x, -1, F, 0, gw, gb, all_drop);
+        const int ub = add_unit(ck1, w1, b1, x, -1, F, 0, gw, gb, all_drop);
         int prev = act(ua, ub, -1);
-        std::vector<int> skips{prev};
+        skips.assign(1, prev);
         const int nconv_down[4] = {2, 3, 3, 3};
         for (int l = 1; l <= 4; ++l) {   // DownTransition (VNet3d.py:46-59)
             const int C = F << l;
@@ -112,12 +127,24 @@ struct Builder {
             int t = down;
             for (int i = 0; i < nconv_down[l - 1]; ++i) {
                 const std::string op = pre + ".ops." + std::to_string(i);
-                const int u = unit(CK_K3, op + ".conv1", true, t, -1, C, l, op + ".bn1");
+                const int u = unit(CK_K3, op + ".conv1", true, t, -1, C, l, op + ".bn1", all_drop);
                 t = act(u, -1, i == nconv_down[l - 1] - 1 ? down : -1);
             }
             prev = t;
             skips.push_back(prev);
         }
+        return prev;
+    }
+
+    void build_resnet() {   // networks/ResNet3d.py:72-118
+        std::vector<int> skips;
+        cls_head(encoder(skips, false), "fc_layers");
+    }
+
+    void build_vnet() {   // networks/VNet3d.py:102-158
+        const int F = e.feat;
+        std::vector<int> skips;
+        int prev = encoder(skips, true);
         skips.pop_back();
         const int nconv_up[4] = {3, 3, 2, 1};
         for (int k = 0; k < 4; ++k) {    // UpTransition (VNet3d.py:62-80): parameter order up_conv, bn, ops, conv
@@ -332,7 +359,7 @@ void launch_halo_conv(const seg_engine& E, int x, int l, const void* in0, const 
 GnFinArgs gn_fin_args(const seg_engine& E, const Step& u) {
     GnFinArgs f{};
     f.stats = (double*)(E.ws + u.stats); f.gamma = E.p + E.params[u.gn_w].off; f.beta = E.p + E.params[u.gn_b].off;
-    f.mask = E.mask_mode == SEG_MASKS_EVAL ? nullptr : E.mask_base(u.mask_slot);
+    f.mask = E.mask_base(u.mask_slot);
     f.mask_ld = E.ld_mask();
     f.scale = (float*)(E.ws + u.scale); f.shift = (float*)(E.ws + u.shift);
     f.mean = (float*)(E.ws + u.mean); f.rstd = (float*)(E.ws + u.rstd);
@@ -345,7 +372,7 @@ GnBwdFinArgs gn_bwd_fin_args(const seg_engine& E, const Step& u) {
     GnBwdFinArgs f{};
     f.Q = (double*)(E.ws + u.Q); f.stats = (double*)(E.ws + u.stats);
     f.gamma = E.p + E.params[u.gn_w].off;
-    f.mask = E.mask_mode == SEG_MASKS_EVAL ? nullptr : E.mask_base(u.mask_slot);
+    f.mask = E.mask_base(u.mask_slot);
     f.mask_ld = E.ld_mask();
     f.mean = (float*)(E.ws + u.mean); f.rstd = (float*)(E.ws + u.rstd);
     f.dgamma = E.g + E.params[u.gn_w].off; f.dbeta = E.g + E.params[u.gn_b].off;
@@ -529,6 +556,28 @@ void fwd_head(seg_engine& E, int si, hipStream_t st) {
     E.prof_end(st, pi);
 }
 
+// classification head: both directions share one argument block (the backward launch reads what the forward launch left in the step's workspace)
+ClsHeadArgs cls_head_args(const seg_engine& E, const Step& s) {
+    ClsHeadArgs a{};
+    a.act = E.ws + E.tens[s.in].off;
+    a.w1 = E.p + E.params[s.w].off; a.b1 = E.p + E.params[s.b].off; a.w2 = E.p + E.params[s.w2].off; a.b2 = E.p + E.params[s.b2].off;
+    a.logits = E.cur_logits; a.probs = E.cur_probs; a.dlogits = E.cur_dlogits;
+    if (E.g) { a.dw1 = E.g + E.params[s.w].off; a.db1 = E.g + E.params[s.b].off; a.dw2 = E.g + E.params[s.w2].off; a.db2 = E.g + E.params[s.b2].off; }
+    a.accumulate = 1;                      // the flat gradient buffer was cleared by the pass (zero_grads) or holds what the caller accumulates onto
+    a.ws = E.ws + s.cls_ws;
+    a.N = E.N; a.C = s.Cout; a.V = E.vol(E.tens[s.in].lvl);
+    return a;
+}
+double cls_head_flops(const ClsHeadArgs& a) { return 2.0 * a.N * ((double)CLS_K * CLS_H + (double)CLS_H * a.C); }
+
+void fwd_cls(seg_engine& E, int si, hipStream_t st) {
+    const Step& s = E.steps[si];
+    const ClsHeadArgs a = cls_head_args(E, s);
+    const int pi = E.prof_begin(st, SEG_K_CLS_HEAD, E.tbytes(s.in) + 4.0 * (CLS_K * CLS_H + CLS_H * a.C), cls_head_flops(a));
+    launch_cls_head_fwd(a, E.dtype, st);
+    E.prof_end(st, pi);
+}
+
 // ------------------------------------------------------------------------------------------------
 // backward launches (gin / gout / gl / draw / g0 / g1: gradient tensor ids fixed by the planner)
 // ------------------------------------------------------------------------------------------------
@@ -542,6 +591,15 @@ void bwd_head(seg_engine& E, int si, int gin, hipStream_t st) {
     a.N = E.N; a.V = (int)E.vol(0); a.Cin = s.Cin; a.C = s.Cout;
     const int pi = E.prof_begin(st, SEG_K_HEAD, E.tbytes(s.in) * (a.din ? 2.0 : 1.0) + 4.0 * E.N * E.vol(0) * s.Cout, 0.0);
     launch_head_bwd(a, E.dtype, st);
+    E.prof_end(st, pi);
+}
+
+void bwd_cls(seg_engine& E, int si, int gin, hipStream_t st) {
+    const Step& s = E.steps[si];
+    ClsHeadArgs a = cls_head_args(E, s);
+    a.dact = E.ws + E.tens[gin].off;
+    const int pi = E.prof_begin(st, SEG_K_CLS_HEAD, E.tbytes(s.in) + 12.0 * (CLS_K * CLS_H + CLS_H * a.C), 3.0 * cls_head_flops(a));
+    launch_cls_head_bwd(a, E.dtype, st);
     E.prof_end(st, pi);
 }
 
@@ -856,6 +914,8 @@ struct Planner {
                 s.rstd = alloc((size_t)N * GN_GROUPS * 4);
                 s.coef = alloc((size_t)N * s.Cout * 3 * 4);
             }
+        for (auto& s : E.steps)
+            if (s.type == ST_CLS) s.cls_ws = alloc(cls_head_ws_bytes(N, E.vol(E.tens[s.in].lvl)));
     }
 
     // packed layouts of one UNIT's weights (forward, data-gradients) and, for halo convs, the conv3x tilings they are packed for
@@ -969,6 +1029,7 @@ struct Planner {
                 case ST_UNIT: E.fwd_ops.push_back([e, si](hipStream_t st) { fwd_unit(*e, si, st); }); break;
                 case ST_ACT:  E.fwd_ops.push_back([e, si](hipStream_t st) { fwd_act(*e, si, st); }); break;
                 case ST_POOL: E.fwd_ops.push_back([e, si](hipStream_t st) { fwd_pool(*e, si, st); }); break;
+                case ST_CLS:  E.fwd_ops.push_back([e, si](hipStream_t st) { fwd_cls(*e, si, st); }); break;
                 default:      E.fwd_ops.push_back([e, si](hipStream_t st) { fwd_head(*e, si, st); }); break;
             }
     }
@@ -989,6 +1050,7 @@ struct Planner {
             bool ok = true;
             switch (E.steps[si].type) {
                 case ST_HEAD: plan_bwd_head(si); break;
+                case ST_CLS:  plan_bwd_cls(si); break;
                 case ST_POOL: ok = plan_bwd_pool(si); break;
                 case ST_ACT:  ok = plan_bwd_act(si); break;
                 default:      ok = plan_bwd_unit(si); break;
@@ -1006,6 +1068,14 @@ struct Planner {
         E.head_step = si;
         E.tens[s.in].grads.push_back(gin);
         push_bwd({s.w, s.b}, [e, si, gin](hipStream_t st) { bwd_head(*e, si, gin, st); });
+    }
+    // the classification head opens the backward pass: its four parameters are registered last, so the finished gradients form a suffix from here on
+    void plan_bwd_cls(int si) {
+        seg_engine* e = &E;
+        const Step& s = E.steps[si];
+        const int gin = new_grad(s.in);
+        E.tens[s.in].grads.push_back(gin);
+        push_bwd({s.w, s.b, s.w2, s.b2}, [e, si, gin](hipStream_t st) { bwd_cls(*e, si, gin, st); });
     }
     bool plan_bwd_pool(int si) {
         seg_engine* e = &E;
@@ -1079,7 +1149,9 @@ struct Planner {
 namespace segi {
 void build_network(seg_engine& e, int net_kind) {
     Builder b(e);
-    if (net_kind == SEG_NET_VNET) b.build_vnet(); else b.build_unet();
+    if (net_kind == SEG_NET_VNET) b.build_vnet();
+    else if (net_kind == SEG_NET_UNET) b.build_unet();
+    else b.build_resnet();
 }
 void plan_engine(seg_engine& e) {
     Planner pl(e);

@@ -93,6 +93,27 @@ struct HeadBwdArgs {
 };
 void launch_head_bwd(const HeadBwdArgs& a, int dtype, hipStream_t s);
 
+// Classification head (cls_head.hip; networks/ResNet3d.py:61-69,91-96): global average pooling over the V voxels of act [N][V][256] T, Linear(256, 128) + ReLU,
+// Linear(128, C); logits / probs [N][C] fp32.  The FC weights are read from the flat fp32 master buffer (PyTorch layout).  `ws` (cls_head_ws_bytes) keeps
+// pooled and h for the backward launch.  Deterministic: no atomics, fixed summation orders (see seg_op_cls_head_forward in include/segengine.h).
+constexpr int CLS_K = 256, CLS_H = 128, CLS_SLAB = 64;      // input channels, hidden units, voxels per pooling workgroup
+struct ClsHeadArgs {
+    const void* act;         // [N][V][CLS_K] T
+    const float* w1; const float* b1; const float* w2; const float* b2;
+    float* logits; float* probs;      // [N][C]
+    // backward
+    const float* dlogits;    // [N][C], times the loss scale
+    float* dw1; float* db1; float* dw2; float* db2;
+    void* dact;              // [N][V][CLS_K] T
+    int accumulate;          // parameter gradients: 1 += , 0 =
+    char* ws;
+    int N, C; long long V;
+};
+size_t cls_head_ws_bytes(int N, long long V);
+size_t cls_head_ws_offset(int N, long long V, int what);      // 0 pooled [N][256], 1 h [N][128], 2 dh [N][128], 3 dpooled [N][256], 4 slab sums fp64 [N][slabs][256]
+void launch_cls_head_fwd(const ClsHeadArgs& a, int dtype, hipStream_t s);
+void launch_cls_head_bwd(const ClsHeadArgs& a, int dtype, hipStream_t s);
+
 // GroupNorm(8) finalize: stats -> per-(n,c) scale/shift (dropout multiplier folded in) + mean/rstd
 struct GnFinArgs {
     const double* stats;  // [N][C][2]

@@ -39,6 +39,7 @@ class SegEngine:
         self.device = torch.device(device)
         self.lib = lib if lib is not None else _capi.lib_for(self.device)
         self.kind, self.ndim, self.in_channels, self.numclass = kind, ndim, in_channels, numclass
+        self.classifier = kind == "resnet"         # logits / probs / dlogits are (N, numclass): the planar layout with one voxel
         self.dtype = dtype
         h = C.c_void_p()
         self.lib.check(self.lib.seg_create(_capi.NET_KIND[kind], ndim, in_channels, numclass, init_features,
@@ -159,10 +160,14 @@ class SegEngine:
         v = 1
         for s in spatial:
             v *= s
-        self.V = v
+        self.V = 1 if self.classifier else v
         self._loss_ws = aligned_empty(self.lib.seg_loss_ws_bytes(int(n), self.numclass), self.device)
         self._out3 = torch.zeros(4, dtype=torch.float32, device=self.device)
-        self._dlogits = torch.empty((int(n), self.numclass) + spatial, dtype=torch.float32, device=self.device)
+        self._dlogits = torch.empty(self.out_shape(n, spatial), dtype=torch.float32, device=self.device)
+
+    def out_shape(self, n, spatial):
+        """shape of logits / probs / dlogits for a batch of n samples"""
+        return (int(n), self.numclass) + (() if self.classifier else tuple(int(s) for s in spatial))
 
     def rebind(self):
         """Re-bind after the caller replaced self.params / self.grads (they must be 256-B aligned)."""
@@ -179,12 +184,12 @@ class SegEngine:
 
     # ---- forward / backward ---------------------------------------------------------------------
     def forward(self, x, mask_mode=_capi.MASKS_EVAL, masks=None, logits=None, probs=None):
-        """x: fp32 NC[D]HW.  Returns (logits, probs) fp32 NC[D]HW."""
+        """x: fp32 NC[D]HW.  Returns (logits, probs) fp32 NC[D]HW ((N, numclass) for the classifiers)."""
         assert x.dtype == torch.float32 and x.is_contiguous() and x.device.type == self.device.type
         self.plan(x.shape[0], x.shape[2:])
         if not self.packed:
             self.pack_weights()
-        oshape = (x.shape[0], self.numclass) + tuple(x.shape[2:])
+        oshape = self.out_shape(x.shape[0], x.shape[2:])
         if logits is None:
             logits = torch.empty(oshape, dtype=torch.float32, device=self.device)
         if probs is None:
@@ -505,7 +510,7 @@ class SegEngine:
         self.plan(x.shape[0], x.shape[2:])
         if self.exp_avg is None:
             self.init_optimizer()
-        oshape = (x.shape[0], self.numclass) + tuple(x.shape[2:])
+        oshape = self.out_shape(x.shape[0], x.shape[2:])
         if logits is None:
             logits = torch.empty(oshape, dtype=torch.float32, device=self.device)
         if probs is None:

@@ -211,3 +211,11 @@ def surface_metrics(real_labels, pred_labels, voxel_spacing, classes, device=Non
                "MSD": np.maximum(o[..., 10], o[..., 11])}
     empty = (r == 0) | (p == 0)
     return {name: np.where(empty, np.nan, res[name]) for name in SURFACE_METRICS}
+
+
+def calc_accuracy(input, target):
+    """model/metric.py:240-243 as written, on the tensors' device: `sum(input == target) / input.size(0)`.  The reference's binary wrappers call it with
+    an (N, 1) tensor of thresholded probabilities and (N,) labels: the comparison BROADCASTS to (N, N) and the count of equal pairs is divided by N, so the
+    value is N x (the agreement rate of all pairs), not the accuracy - reproduced, not repaired (the multi-class form compares (N,) with (N,))."""
+    n = input.size(0)
+    return torch.sum(input == target).sum().float() / n

@@ -1,6 +1,7 @@
 """`networks` boundary: VNet3d / VNet2d / UNet3d / UNet2d as nn.Modules with the
 reference's constructor signatures, `forward(x) -> (logits, probs)` and bit-compatible `state_dict`
-keys/shapes (networks/VNet3d.py:102-158, VNet2d.py, Unet3d.py:6-86, Unet2d.py of the reference), so
+keys/shapes (networks/VNet3d.py:102-158, VNet2d.py, Unet3d.py:6-86, Unet2d.py of the reference), and the
+classifiers ResNet3d / ResNet2d (networks/ResNet3d.py:72-118, ResNet2d.py; `forward(x) -> logits (N, numclass)`), so
 old `.pth` files load and `model.apply(initialize_weights)` keeps working.  The sub-modules are real
 nn.Conv / nn.ConvTranspose / nn.GroupNorm objects that only HOLD parameters — their tensors are views
 into the engine's flat fp32 buffer; all arithmetic runs in libsegengine (HIP, gfx950)."""
@@ -18,7 +19,9 @@ def _default_dtype():
 
 
 class _Container(nn.Module):
-    pass
+    def __getitem__(self, i):
+        """children named by their index (`fc_layers[0]`, `ops[1]`), as in the reference's nn.Sequential containers"""
+        return getattr(self, str(i))
 
 
 class _NetFn(torch.autograd.Function):
@@ -74,6 +77,8 @@ class _SegNet(nn.Module):
             has_bias = (leaf + ".bias") in table
             if len(wshape) == 1:
                 mod = nn.GroupNorm(8, wshape[0])
+            elif len(wshape) == 2:
+                mod = nn.Linear(wshape[1], wshape[0])
             else:
                 k = wshape[2]
                 last = leaf.rsplit(".", 1)[-1]
@@ -177,6 +182,34 @@ class UNet2d(_SegNet):
     def __init__(self, in_channels, out_channels, init_features=16, dtype=None):
         super().__init__(in_channels, out_channels, init_features, dtype)
         self.in_channels, self.out_channels = in_channels, out_channels
+
+
+class _ClsNet(_SegNet):
+    """The classifiers: the VNet encoder, global average pooling and two FC layers (SEG_NET_RESNET).  `forward` returns ONE tensor, the logits
+    (N, numclass), as the reference does; `.train()` makes the engine draw the four channel-dropout masks (behind each down_conv, p = 0.2: the
+    reference reads an undefined global `prob` there and cannot be constructed as shipped - the VNet value is used)."""
+    _kind = "resnet"
+
+    def __init__(self, image_channel, numclass, dtype=None):
+        super().__init__(image_channel, numclass, 16, dtype)
+        self.image_channel, self.numclass = image_channel, numclass
+
+    def forward(self, x):
+        return super().forward(x)[0]
+
+    def forward_probs(self, x):
+        """(logits, probs): probs = sigmoid (numclass == 1) / soft-max of the logits, from the same launch"""
+        return super().forward(x)
+
+
+class ResNet3d(_ClsNet):
+    """networks/ResNet3d.py:72-118"""
+    _ndim = 3
+
+
+class ResNet2d(_ClsNet):
+    """networks/ResNet2d.py"""
+    _ndim = 2
 
 
 def initialize_weights(net):

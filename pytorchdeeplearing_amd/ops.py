@@ -493,3 +493,38 @@ def maxpool(x, window, dtype, dout=None):
     lib.check(lib.seg_op_maxpool(x.data_ptr(), None, dout.data_ptr(), din.data_ptr(), N, D, H, W, C_, pd, ph, pw, 1, _capi.DTYPE[dtype],
                                  _capi.stream_for(x.device)), "seg_op_maxpool")
     return din
+
+
+def cls_head_forward(act, w1, b1, w2, b2, dtype):
+    """classification head on act [N, V, 256] (run dtype): returns dict(logits, probs (N, C) fp32, pooled (N, 256), h (N, 128) fp32 views of `ws`, ws);
+    hand the dict to cls_head_backward"""
+    lib = _capi.lib_for(act.device)
+    N, V, K = act.shape
+    assert K == 256 and act.dtype == TORCH_DTYPE[dtype] and act.is_contiguous()
+    C_ = w2.shape[0]
+    nbytes = lib.seg_op_cls_head_ws_bytes(N, V)
+    lib.check(nbytes, "seg_op_cls_head_ws_bytes")
+    ws = aligned_empty(nbytes, act.device)
+    logits = _alloc((N, C_), torch.float32, act.device)
+    probs = _alloc((N, C_), torch.float32, act.device)
+    lib.check(lib.seg_op_cls_head_forward(act.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), logits.data_ptr(), probs.data_ptr(),
+                                          N, V, C_, ws.data_ptr(), _capi.DTYPE[dtype], _capi.stream_for(act.device)), "seg_op_cls_head_forward")
+    o0, o1 = lib.seg_op_cls_head_ws_offset(N, V, 0), lib.seg_op_cls_head_ws_offset(N, V, 1)
+    return dict(logits=logits, probs=probs, pooled=ws[o0:o0 + N * 256 * 4].view(torch.float32).view(N, 256),
+                h=ws[o1:o1 + N * 128 * 4].view(torch.float32).view(N, 128), ws=ws, shape=(N, V, C_), keep=(act, w1, b1, w2, b2))
+
+
+def cls_head_backward(fwd, dlogits, w1, w2, dtype, grads=None, zero_grads=True):
+    """backward of cls_head_forward: returns dict(dw1, db1, dw2, db2 fp32, dact [N, V, 256] run dtype).  grads: dict of the four gradient buffers to write /
+    accumulate into (zero_grads = False: added to what they hold)"""
+    ws = fwd["ws"]
+    lib = _capi.lib_for(ws.device)
+    N, V, C_ = fwd["shape"]
+    g = grads if grads is not None else dict(dw1=_alloc((128, 256), torch.float32, ws.device, zero=True), db1=_alloc((128,), torch.float32, ws.device, zero=True),
+                                             dw2=_alloc((C_, 128), torch.float32, ws.device, zero=True), db2=_alloc((C_,), torch.float32, ws.device, zero=True))
+    dact = _alloc((N, V, 256), TORCH_DTYPE[dtype], ws.device)
+    assert dlogits.dtype == torch.float32 and dlogits.is_contiguous() and tuple(dlogits.shape) == (N, C_)
+    lib.check(lib.seg_op_cls_head_backward(dlogits.data_ptr(), w1.data_ptr(), w2.data_ptr(), g["dw1"].data_ptr(), g["db1"].data_ptr(), g["dw2"].data_ptr(),
+                                           g["db2"].data_ptr(), dact.data_ptr(), N, V, C_, 1 if zero_grads else 0, ws.data_ptr(), _capi.DTYPE[dtype],
+                                           _capi.stream_for(ws.device)), "seg_op_cls_head_backward")
+    return dict(g, dact=dact)
