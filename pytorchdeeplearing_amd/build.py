@@ -7,6 +7,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libsegengine.so")
 SRCS = ["conv.hip", "conv3.hip", "conv3x.hip", "conv3x_f16_3d.hip", "conv3x_f16_2d.hip", "conv3x_bf16_3d.hip", "conv3x_bf16_2d.hip", "wgrad.hip", "stemx.hip", "norm.hip", "misc.hip", "cls_head.hip", "lovasz.hip", "ssim.hip", "cldice.hip", "surface.hip", "augment.hip", "postproc.hip", "prepost.hip", "engine.hip", "engine_plan.hip", "capi_ops.hip"]
+# every project header: the build id and the freshness checks cover all of them (tests/emu/build_emu.py uses the same list)
+HDRS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(os.path.dirname(HERE), "include", "segengine.h")]
 ID_UNIT = "engine.hip"          # compiled with -DSEG_BUILD_ID
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -munsafe-fp-atomics: fp32 / fp64 atomicAdd as the hardware instruction instead of a compare-and-swap loop (every buffer the library adds into is ordinary
@@ -27,9 +29,7 @@ def build_id():
 
 
 def _deps():
-    d = [os.path.join(CSRC, f) for f in SRCS + ["common.h", "kernels.h", "conv3x_impl.h", "gn_fold.h", "engine_internal.h"]]
-    d.append(os.path.join(os.path.dirname(HERE), "include", "segengine.h"))
-    return d
+    return [os.path.join(CSRC, f) for f in SRCS] + HDRS
 
 
 def up_to_date():
@@ -65,8 +65,7 @@ def build(force=False, verbose=False):
     os.makedirs(os.path.join(HERE, "lib"), exist_ok=True)
     objdir = os.path.join(HERE, "lib", "obj")
     os.makedirs(objdir, exist_ok=True)
-    hdrs = [os.path.join(CSRC, h) for h in ("common.h", "kernels.h", "conv3x_impl.h", "gn_fold.h", "engine_internal.h")] + [os.path.join(os.path.dirname(HERE), "include", "segengine.h")]
-    hdr_t = max(os.path.getmtime(h) for h in hdrs)
+    hdr_t = max(os.path.getmtime(h) for h in HDRS)
     procs, objs = [], []
     bid = build_id()
     for s in SRCS:

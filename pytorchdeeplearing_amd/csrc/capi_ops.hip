@@ -4,6 +4,9 @@
 
 #include "engine_internal.h"
 
+// the status of an entry point that ends in a launch
+#define SEG_OK(what) (hipGetLastError() == hipSuccess ? 0 : fail(what ": launch failed"))
+
 extern "C" {
 
 long long seg_loss_ws_bytes(int n, int c) { return (long long)align_up(loss_sums_count(n, c) * sizeof(double) * STAT_REP); }
@@ -33,7 +36,7 @@ int seg_loss_forward(const float* logits, const void* target, int label_type, in
     if (!out3) return fail("seg_loss_forward: out3 is null");
     a.class_alpha = class_alpha; a.out = out3;
     launch_loss_forward(a, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_loss_forward: launch failed");
+    return SEG_OK("seg_loss_forward");
 }
 
 int seg_loss_shared_doubles(void) { return loss_shared_count(); }
@@ -44,7 +47,7 @@ int seg_loss_reduce(const float* logits, const void* target, int label_type, int
     if (fill_loss(a, logits, target, label_type, n, c, v, loss_kind, focal_alpha, focal_gamma, ws)) return -1;
     a.phase = 1;
     launch_loss_forward(a, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_loss_reduce: launch failed");
+    return SEG_OK("seg_loss_reduce");
 }
 
 int seg_loss_finalize(const float* logits, const void* target, int label_type, int n, int c, long long v, int loss_kind,
@@ -55,7 +58,7 @@ int seg_loss_finalize(const float* logits, const void* target, int label_type, i
     if (n_global != 0 && n_global < n) return fail("seg_loss_finalize: n_global must be >= the local sample count (or 0: the exchanged count)");
     a.class_alpha = class_alpha; a.out = out3; a.phase = 2; a.n_global = n_global;
     launch_loss_forward(a, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_loss_finalize: launch failed");
+    return SEG_OK("seg_loss_finalize");
 }
 
 int seg_loss_backward(const float* logits, const void* target, int label_type, int n, int c, long long v, int loss_kind,
@@ -65,7 +68,7 @@ int seg_loss_backward(const float* logits, const void* target, int label_type, i
     if (!dlogits) return fail("seg_loss_backward: dlogits is null");
     a.dlogits = dlogits; a.grad_scale = grad_scale;
     launch_loss_backward(a, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_loss_backward: launch failed");
+    return SEG_OK("seg_loss_backward");
 }
 
 long long seg_lovasz_ws_bytes(int n, long long v) {
@@ -79,7 +82,7 @@ int seg_lovasz_forward(const float* x, const void* target, int label_type, int n
     if (n < 1 || v < 1 || c < 1 || c > 16) return fail("seg_lovasz_forward: classes must be 1..16, batch and volume non-empty");
     if ((long long)n * v >= (1ll << 32)) return fail("seg_lovasz_forward: element count must be below 2^32");
     if (launch_lovasz(x, target, label_type, n, c, v, ws, out1, dx, (hipStream_t)stream)) return fail("seg_lovasz_forward: sort / scan failed");
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_lovasz_forward: launch failed");
+    return SEG_OK("seg_lovasz_forward");
 }
 
 static int ssim_check(const char* what, const void* a, const void* b, const void* ws, int n, int c, int d, int h, int w, int nd, int window) {
@@ -93,7 +96,7 @@ int seg_ssim_forward(const float* img1, const float* img2, int n, int c, int d, 
                      void* stream) {
     if (ssim_check("seg_ssim_forward", img1, img2, ws, n, c, d, h, w, nd, window) || !out) return out ? -1 : fail("seg_ssim_forward: out is null");
     if (launch_ssim_forward(img1, img2, n, c, nd == 3 ? d : 1, h, w, nd, window, ws, out, (hipStream_t)stream)) return fail("seg_ssim_forward: bad arguments");
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_ssim_forward: launch failed");
+    return SEG_OK("seg_ssim_forward");
 }
 int seg_ssim_forward_cols(const float* img1, const float* img2, int n, int c, int d, int h, int w, int nd, int window, void* ws, float* out,
                           float* out_cols, void* stream) {
@@ -101,7 +104,7 @@ int seg_ssim_forward_cols(const float* img1, const float* img2, int n, int c, in
         return (out && out_cols) ? -1 : fail("seg_ssim_forward_cols: out is null");
     if (launch_ssim_forward(img1, img2, n, c, nd == 3 ? d : 1, h, w, nd, window, ws, out, (hipStream_t)stream, out_cols))
         return fail("seg_ssim_forward_cols: bad arguments");
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_ssim_forward_cols: launch failed");
+    return SEG_OK("seg_ssim_forward_cols");
 }
 int seg_ssim_backward(const float* img1, const float* img2, int n, int c, int d, int h, int w, int nd, int window, void* ws, const float* gscale,
                       int per_sample, float* dimg1, float* dimg2, void* stream) {
@@ -109,14 +112,14 @@ int seg_ssim_backward(const float* img1, const float* img2, int n, int c, int d,
     if (!gscale || (!dimg1 && !dimg2)) return fail("seg_ssim_backward: null pointer");
     if (launch_ssim_backward(img1, img2, n, c, nd == 3 ? d : 1, h, w, nd, window, ws, gscale, per_sample, dimg1, dimg2, (hipStream_t)stream))
         return fail("seg_ssim_backward: bad arguments");
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_ssim_backward: launch failed");
+    return SEG_OK("seg_ssim_backward");
 }
 
 int seg_predict_mask(const float* probs, unsigned char* mask, int n, int c, long long v, float threshold, int scale, void* stream) {
     if (!probs || !mask) return fail("seg_predict_mask: null pointer");
     if (c < 1 || n < 1 || v < 1 || scale < 0 || scale > 255) return fail("seg_predict_mask: bad arguments");
     launch_mask(probs, mask, n, c, v, threshold, scale, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_predict_mask: launch failed");
+    return SEG_OK("seg_predict_mask");
 }
 int seg_op_resample3d(const void* src, void* dst, int elem_type, int sd, int sh, int sw, int dd, int dh, int dw, double step_z, double step_y,
                       double step_x, int mode, void* stream) {
@@ -130,7 +133,7 @@ int seg_op_resample3d(const void* src, void* dst, int elem_type, int sd, int sh,
     a.src = src; a.dst = dst; a.sD = sd; a.sH = sh; a.sW = sw; a.dD = dd; a.dH = dh; a.dW = dw;
     a.fz = step_z; a.fy = step_y; a.fx = step_x; a.mode = mode;
     launch_resample3d(a, elem_type, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_resample3d: launch failed");
+    return SEG_OK("seg_op_resample3d");
 }
 long long seg_op_normalize_ws_bytes(void) { return (long long)normalize_ws_bytes(); }
 int seg_op_normalize_meanstd(const float* x, float* out, long long n, int clip, float lower, float upper, void* ws, void* stream) {
@@ -138,14 +141,14 @@ int seg_op_normalize_meanstd(const float* x, float* out, long long n, int clip, 
     if (n < 1) return fail("seg_op_normalize_meanstd: empty volume");
     if (clip && !(lower <= upper)) return fail("seg_op_normalize_meanstd: lower > upper");
     launch_normalize_meanstd(x, out, n, clip, lower, upper, ws, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_normalize_meanstd: launch failed");
+    return SEG_OK("seg_op_normalize_meanstd");
 }
 int seg_op_normalize_percentile(const float* x, float* out, long long n, float q_lo, float q_hi, void* ws, void* stream) {
     if (!x || !out || !ws) return fail("seg_op_normalize_percentile: null pointer");
     if (n < 1) return fail("seg_op_normalize_percentile: empty volume");
     if (!(q_lo >= 0.f && q_lo <= q_hi && q_hi <= 100.f)) return fail("seg_op_normalize_percentile: need 0 <= q_lo <= q_hi <= 100");
     launch_normalize_percentile(x, out, n, q_lo, q_hi, ws, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_normalize_percentile: launch failed");
+    return SEG_OK("seg_op_normalize_percentile");
 }
 static int check_windows(const char* what, int D, int H, int W, int nb, int pd, int ph, int pw) {
     if (nb < 1 || pd < 1 || ph < 1 || pw < 1) return fail(std::string(what) + ": empty patch list");
@@ -156,21 +159,21 @@ int seg_op_gather_patches(const float* vol, int d, int h, int w, const int* orig
     if (!vol || !origins || !out) return fail("seg_op_gather_patches: null pointer");
     if (check_windows("seg_op_gather_patches", d, h, w, nb, pd, ph, pw)) return -1;
     launch_gather_patches(vol, d, h, w, origins, nb, pd, ph, pw, out, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_gather_patches: launch failed");
+    return SEG_OK("seg_op_gather_patches");
 }
 int seg_op_stitch_mask(const unsigned char* masks, const int* origins, int nb, int pd, int ph, int pw, unsigned char* out, int d, int h, int w,
                        void* stream) {
     if (!masks || !origins || !out) return fail("seg_op_stitch_mask: null pointer");
     if (check_windows("seg_op_stitch_mask", d, h, w, nb, pd, ph, pw)) return -1;
     launch_stitch_mask(masks, origins, nb, pd, ph, pw, out, d, h, w, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_stitch_mask: launch failed");
+    return SEG_OK("seg_op_stitch_mask");
 }
 
 int seg_metric(const float* probs, const void* target, int label_type, int n, int c, long long v, void* ws, float* out2, void* stream) {
     if (!probs || !target || !ws || !out2) return fail("seg_metric: null pointer");
     if (c < 1 || c > 16) return fail("seg_metric: classes must be 1..16");
     launch_metric(probs, target, label_type, n, c, v, (double*)ws, out2, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_metric: launch failed");
+    return SEG_OK("seg_metric");
 }
 
 
@@ -187,7 +190,7 @@ int seg_surface_metrics(const unsigned char* real, const unsigned char* pred, in
     if (!surface_extents_ok(d, h, w)) return fail("seg_surface_metrics: extents must be 1..2048 with d*h*w < 2^31");
     if (cls < -1 || cls > 255) return fail("seg_surface_metrics: cls must be -1 (label != 0) or a label value 0..255");
     launch_surface_metrics(real, pred, d, h, w, cls, sz, sy, sx, ws, out16, real2pred_nn, pred2real_nn, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_surface_metrics: launch failed");
+    return SEG_OK("seg_surface_metrics");
 }
 
 
@@ -237,7 +240,7 @@ int seg_augment3d(const float* x, float* out, int n, int c, int n0, int n1, int 
     a.extrema = extrema != 0;
     a.has_scale = !a.extrema && rescale != 0.0; a.scale = (float)rescale;
     launch_augment3d(a, label_type, ws, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_augment3d: launch failed");
+    return SEG_OK("seg_augment3d");
 }
 int seg_augment3d_shift(float* x, int n, int c, int n0, int n1, int n2, long long xs_c, long long xs_v, const double* params_dev, double rescale,
                         const void* ws, void* stream) {
@@ -249,7 +252,7 @@ int seg_augment3d_shift(float* x, int n, int c, int n0, int n1, int n2, long lon
     if (!std::isfinite(rescale)) return fail("seg_augment3d_shift: rescale must be finite");
     if (!params_dev && rescale == 0.0) return 0;
     launch_augment3d_shift(x, n, c, (long long)n0 * n1 * n2, xs_c, xs_v, params_dev, ws, (float)rescale, rescale != 0.0, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_augment3d_shift: launch failed");
+    return SEG_OK("seg_augment3d_shift");
 }
 
 
@@ -267,7 +270,7 @@ int seg_cc_label(const unsigned char* mask, int n, int d, int h, int w, int cls,
     if (cls < -1 || cls > 255) return fail("seg_cc_label: cls must be -1 (value != 0) or a value 0..255");
     if (connectivity != 1 && connectivity != 3) return fail("seg_cc_label: connectivity must be 1 (faces) or 3 (fully connected)");
     launch_cc_label(mask, n, d, h, w, cls, connectivity, ws, labels, stats, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_cc_label: launch failed");
+    return SEG_OK("seg_cc_label");
 }
 int seg_cc_filter(const unsigned char* mask, unsigned char* out, int n, int d, int h, int w, int cls, int connectivity, int mode, long long min_voxels,
                   void* ws, int* stats, void* stream) {
@@ -278,7 +281,7 @@ int seg_cc_filter(const unsigned char* mask, unsigned char* out, int n, int d, i
     if (mode != SEG_CC_KEEP_LARGEST && mode != SEG_CC_MIN_SIZE) return fail("seg_cc_filter: unknown mode");
     if (mode == SEG_CC_MIN_SIZE && min_voxels < 0) return fail("seg_cc_filter: min_voxels must not be negative");
     launch_cc_filter(mask, out, n, d, h, w, cls, connectivity, mode, min_voxels, ws, stats, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_cc_filter: launch failed");
+    return SEG_OK("seg_cc_filter");
 }
 long long seg_morph3d_ws_bytes(int n, int d, int h, int w) {
     if (!postproc_extents_ok(n, d, h, w)) return fail(std::string("seg_morph3d_ws_bytes: ") + POSTPROC_EXTENTS);
@@ -296,7 +299,7 @@ int seg_morph3d(const unsigned char* mask, unsigned char* out, int n, int d, int
     if ((op == SEG_MORPH_OPEN || op == SEG_MORPH_CLOSE) && border != -1) return fail("seg_morph3d: open and close take no explicit border");
     if (fg_value < 0 || fg_value > 255) return fail("seg_morph3d: fg_value must be 0..255");
     launch_morph3d(mask, out, n, d, h, w, cls, op, shape, rz, ry, rx, border, fg_value, ws, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_morph3d: launch failed");
+    return SEG_OK("seg_morph3d");
 }
 
 }  // extern "C"
@@ -314,7 +317,7 @@ int adam_step_impl(float* params, const float* grads, float* exp_avg, float* exp
     if (!riders) (void)hipMemsetAsync(state + 1, 0, sizeof(int), st);
     if (check_finite) launch_grad_check(grads, numel, state + 1, st);
     launch_adam(a, st, !riders);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_adam_step: launch failed");
+    return SEG_OK("seg_adam_step");
 }
 }  // namespace segi
 extern "C" {
@@ -334,7 +337,7 @@ int seg_op_conv(const seg_conv_args* a, int dtype, void* stream) {
     if (a->rq_Q && !(a->out1 && conv_uses_stream_kernel(*a))) return fail("seg_op_conv: rq_* need out1 / Cout0 on the streaming kernel and all of rq_r, rq_scale, rq_shift");
     if (a->out1 && !conv_uses_stream_kernel(*a)) return fail("seg_op_conv: out1 / Cout0 need the streaming kernel (gather form, no bias / stats, 16-channel tiles in pairs)");
     launch_conv_igemm(*a, dtype, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_conv: launch failed");
+    return SEG_OK("seg_op_conv");
 }
 int seg_op_conv_kernel(const seg_conv_args* a) { return a ? (conv_uses_stream_kernel(*a) ? 1 : 0) : -1; }
 long long seg_op_wgrad_partial_bytes(const seg_wgrad_args* a) { return a ? (long long)wgrad_partial_bytes(*a) : -1; }
@@ -345,19 +348,19 @@ int seg_op_wgrad(const seg_wgrad_args* a, float* partial_scratch, int dtype, voi
     if ((a->act_scale || a->act_shift) && !(a->act_scale && a->act_shift && dtype != SEG_F32 && wgrad_act_supported(*a)))
         return fail("seg_op_wgrad: act_scale / act_shift need a 1^d stride-1 conv on 16-bit tensors with C0 <= 64 and come as a pair");
     launch_wgrad(*a, partial_scratch, dtype, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_wgrad: launch failed");
+    return SEG_OK("seg_op_wgrad");
 }
 int seg_op_pack(const seg_pack_desc* descs, int ndesc, long long max_elems, int dtype, void* stream) {
     if (!descs || ndesc < 1) return fail("seg_op_pack: no descriptors");
     launch_pack(descs, ndesc, (int)max_elems, dtype, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_pack: launch failed");
+    return SEG_OK("seg_op_pack");
 }
 int seg_op_conv3(const void* in, const void* w, const float* bias, void* out, double* stats, int n, int d, int h, int wid, int cin,
                  int cout, int ndim, int dtype, void* stream) {
     if (!in || !w || !out) return fail("seg_op_conv3: null pointer");
     if (cin < 16 || (cin & (cin - 1)) || cout % 16) return fail("seg_op_conv3: Cin must be a power of two >= 16, Cout a multiple of 16");
     launch_conv3(in, w, bias, out, stats, n, ndim == 3 ? d : 1, h, wid, cin, cout, ndim, dtype, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_conv3: launch failed");
+    return SEG_OK("seg_op_conv3");
 }
 int seg_op_conv3x(int cfg, const void* in0, const void* in1, int c0, const void* w, const float* bias, void* out, double* stats, int n, int d,
                   int h, int wid, int cin, int cout, int ndim, int dtype, void* stream) {
@@ -369,7 +372,7 @@ int seg_op_conv3x(int cfg, const void* in0, const void* in1, int c0, const void*
     if (cfg < 0) cfg = conv3x_pick(ndim, n, dd, h, wid, cin, cout);
     if (cfg < 0 || !launch_conv3x(cfg, in0, in1, c0, w, bias, out, stats, n, dd, h, wid, cin, cout, ndim, dtype, (hipStream_t)stream))
         return fail("seg_op_conv3x: the tiling does not fit this shape");
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_conv3x: launch failed");
+    return SEG_OK("seg_op_conv3x");
 }
 int seg_op_conv3x_num_cfgs(void) { return conv3x_num_cfgs(); }
 int seg_op_conv3x_cfg_frag(int cfg) { return conv3x_cfg_frag(cfg); }
@@ -392,7 +395,7 @@ int seg_op_wgrad3(const void* dr, const void* x, float* partial, float* dw, int 
     if (!dr || !x || !partial || !dw) return fail("seg_op_wgrad3: null pointer");
     if (p % 16 || q % 16 || (p > 16 && p % 32) || (q > 16 && q % 32)) return fail("seg_op_wgrad3: channel counts must be 16 or multiples of 32");
     launch_wgrad3(dr, x, partial, dw, n, ndim == 3 ? d : 1, h, wid, p, q, ndim, dtype, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_wgrad3: launch failed");
+    return SEG_OK("seg_op_wgrad3");
 }
 int seg_op_wgrad3_cat(const void* dr, const void* x0, const void* x1, int c0, float* partial, float* dw, int n, int d, int h, int wid, int p,
                       int q, int ndim, int dtype, void* stream) {
@@ -400,7 +403,7 @@ int seg_op_wgrad3_cat(const void* dr, const void* x0, const void* x1, int c0, fl
     if (p % 16 || q % 16 || (p > 16 && p % 32) || (q > 16 && q % 32)) return fail("seg_op_wgrad3_cat: channel counts must be 16 or multiples of 32");
     if (c0 <= 0 || c0 >= q || c0 % 16) return fail("seg_op_wgrad3_cat: c0 must be a multiple of 16 inside (0, q)");
     launch_wgrad3(dr, x0, partial, dw, n, ndim == 3 ? d : 1, h, wid, p, q, ndim, dtype, (hipStream_t)stream, x1, c0);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_wgrad3_cat: launch failed");
+    return SEG_OK("seg_op_wgrad3_cat");
 }
 long long seg_op_stemx_partial_bytes(int ndim, int n, int d, int h, int wid, int cimg) {
     return (long long)stemx_partial_bytes(ndim, n, ndim == 3 ? d : 1, h, wid, cimg);
@@ -418,7 +421,7 @@ int seg_op_stemx(const seg_stemx_args* a, int mode, int ndim, int dtype, float* 
     if (mode == 2 && (!a->Q3 || (a->w1 && !a->Q1))) return fail("seg_op_stemx: Q pointers");
     if (mode == 3 && (!a->coef3 || (a->w1 && !a->coef1) || !a->partial || !dw3 || (a->w1 && !dw1))) return fail("seg_op_stemx: weight-gradient pointers");
     launch_stemx(*a, mode, ndim, dtype, dw3, dw1, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_stemx: launch failed");
+    return SEG_OK("seg_op_stemx");
 }
 int seg_abi_sizeof(int which) {
     return which == 0 ? (int)sizeof(seg_conv_args) : which == 1 ? (int)sizeof(seg_wgrad_args) : which == 2 ? (int)sizeof(seg_pack_desc)
@@ -461,7 +464,7 @@ int seg_op_gn_forward(const seg_gn_fwd_args* a, int dtype, void* stream) {
         if (a->r2) return fail("seg_op_gn_forward: the one-workgroup-per-group form has no second branch");
         if (!gn_bwd_group_eligible(a->C, a->V, esz)) return fail("seg_op_gn_forward: shape not eligible for the one-workgroup-per-group form (C >= 64, <= 128 KB per sample)");
         launch_gn_fwd_group(f1, a->r1, a->res, a->out, dtype, st);
-        return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_gn_forward: launch failed");
+        return SEG_OK("seg_op_gn_forward");
     }
     ActArgs x{};
     x.r1 = a->r1; x.scale1 = a->scale1; x.shift1 = a->shift1;
@@ -473,7 +476,7 @@ int seg_op_gn_forward(const seg_gn_fwd_args* a, int dtype, void* stream) {
     } else if (a->r2) launch_gn_finalize(f1, st, &f2);
     else launch_gn_finalize(f1, st);
     launch_gn_act(x, dtype, st);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_gn_forward: launch failed");
+    return SEG_OK("seg_op_gn_forward");
 }
 
 int seg_op_gn_backward(const seg_gn_bwd_args* a, int dtype, void* stream) {
@@ -521,7 +524,7 @@ int seg_op_gn_backward(const seg_gn_bwd_args* a, int dtype, void* stream) {
             launch_gn_bwd_apply(e, dtype, st);
         } else launch_gn_bwd_apply(e, dtype, st, &f, a->r2 ? &f2 : nullptr);
     }
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_gn_backward: launch failed");
+    return SEG_OK("seg_op_gn_backward");
 }
 
 int seg_op_gn_coop_plan(int c, long long v, int n, int esz, int* S, int* ku) {
@@ -540,7 +543,7 @@ int seg_op_maxpool(const void* in, void* out, const void* dout, void* din, int n
     a.in = in; a.out = out; a.dout = dout; a.din = din; a.N = n; a.D = d; a.H = h; a.W = w; a.C = c; a.pd = pd; a.ph = ph; a.pw = pw;
     if (backward) launch_maxpool_bwd(a, dtype, (hipStream_t)stream);
     else launch_maxpool_fwd(a, dtype, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_maxpool: launch failed");
+    return SEG_OK("seg_op_maxpool");
 }
 
 static int cls_head_extents_ok(int n, long long v, int c) { return n >= 1 && n <= 65535 && v >= 1 && v < (1ll << 31) / CLS_K && c >= 1 && c <= 16; }
@@ -561,7 +564,7 @@ int seg_op_cls_head_forward(const void* act, const float* w1, const float* b1, c
     ClsHeadArgs a{};
     a.act = act; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.logits = logits; a.probs = probs; a.N = n; a.V = v; a.C = c; a.ws = (char*)ws;
     launch_cls_head_fwd(a, dtype, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_cls_head_forward: launch failed");
+    return SEG_OK("seg_op_cls_head_forward");
 }
 int seg_op_cls_head_backward(const float* dlogits, const float* w1, const float* w2, float* dw1, float* db1, float* dw2, float* db2, void* dact, int n,
                              long long v, int c, int zero_grads, void* ws, int dtype, void* stream) {
@@ -573,10 +576,9 @@ int seg_op_cls_head_backward(const float* dlogits, const float* w1, const float*
     a.dlogits = dlogits; a.w1 = w1; a.w2 = w2; a.dw1 = dw1; a.db1 = db1; a.dw2 = dw2; a.db2 = db2; a.dact = dact; a.accumulate = zero_grads ? 0 : 1;
     a.N = n; a.V = v; a.C = c; a.ws = (char*)ws;
     launch_cls_head_bwd(a, dtype, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : fail("seg_op_cls_head_backward: launch failed");
+    return SEG_OK("seg_op_cls_head_backward");
 }
 
-#define SEG_OK(what) (hipGetLastError() == hipSuccess ? 0 : fail(what ": launch failed"))
 int seg_op_pool3(const float* x, float* out, int planes, int d, int h, int w, int nd, int is_min, void* stream) {
     if (!x || !out || (nd != 2 && nd != 3)) return fail("seg_op_pool3: bad arguments");
     launch_pool3(x, out, planes, d, h, w, nd, is_min, (hipStream_t)stream);

@@ -9,6 +9,7 @@
 //   * sums over samples (parameter gradients): ascending n in one thread.
 // The FC weights are read from the flat fp32 master buffer in PyTorch's [out][in] layout - nothing is packed for this head.
 #include "kernels.h"
+#include "dispatch.h"
 
 namespace seg {
 
@@ -154,9 +155,10 @@ void launch_cls_head_fwd(const ClsHeadArgs& a, int dtype, hipStream_t s) {
     float* pooled = (float*)(a.ws + cls_head_ws_offset(a.N, a.V, 0));
     float* h = (float*)(a.ws + cls_head_ws_offset(a.N, a.V, 1));
     const dim3 grid(nslab, a.N);
-    if (dtype == DT_F32) hipLaunchKernelGGL(HIP_KERNEL_NAME(cls_pool_kernel<float>), grid, dim3(CLS_K), 0, s, (const float*)a.act, slab, a.V, nslab);
-    else if (dtype == DT_F16) hipLaunchKernelGGL(HIP_KERNEL_NAME(cls_pool_kernel<f16>), grid, dim3(CLS_K), 0, s, (const f16*)a.act, slab, a.V, nslab);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(cls_pool_kernel<bf16>), grid, dim3(CLS_K), 0, s, (const bf16*)a.act, slab, a.V, nslab);
+    by_dtype(dtype, [&](auto t) {
+        using T = tag_type<decltype(t)>;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(cls_pool_kernel<T>), grid, dim3(CLS_K), 0, s, (const T*)a.act, slab, a.V, nslab);
+    });
     hipLaunchKernelGGL(cls_fc_fwd_kernel, dim3(a.N), dim3(CLS_K), 0, s, (const double*)slab, nslab, a.V, a.w1, a.b1, a.w2, a.b2, pooled, h, a.logits, a.probs,
                        a.C);
 }
@@ -170,9 +172,10 @@ void launch_cls_head_bwd(const ClsHeadArgs& a, int dtype, hipStream_t s) {
     hipLaunchKernelGGL(cls_bwd_param_kernel, dim3(CLS_H + a.C), dim3(CLS_K), 0, s, a.dlogits, pooled, h, (const float*)dh, a.dw1, a.db1, a.dw2, a.db2, a.N,
                        a.C, a.accumulate);
     const dim3 grid(cls_slabs(a.V), a.N);
-    if (dtype == DT_F32) hipLaunchKernelGGL(HIP_KERNEL_NAME(cls_bwd_spread_kernel<float>), grid, dim3(CLS_K), 0, s, (const float*)dpooled, (float*)a.dact, a.V);
-    else if (dtype == DT_F16) hipLaunchKernelGGL(HIP_KERNEL_NAME(cls_bwd_spread_kernel<f16>), grid, dim3(CLS_K), 0, s, (const float*)dpooled, (f16*)a.dact, a.V);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(cls_bwd_spread_kernel<bf16>), grid, dim3(CLS_K), 0, s, (const float*)dpooled, (bf16*)a.dact, a.V);
+    by_dtype(dtype, [&](auto t) {
+        using T = tag_type<decltype(t)>;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(cls_bwd_spread_kernel<T>), grid, dim3(CLS_K), 0, s, (const float*)dpooled, (T*)a.dact, a.V);
+    });
 }
 
 }  // namespace seg

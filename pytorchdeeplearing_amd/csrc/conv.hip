@@ -9,6 +9,7 @@
 #include <cstdlib>
 
 #include "kernels.h"
+#include "dispatch.h"
 
 namespace seg {
 
@@ -243,22 +244,12 @@ void conv_dispatch(const ConvArgs& a, hipStream_t s, int srep) {
     // two reduction slices per stage where the launch is a latency chain (fewer than two workgroups per CU) and K allows it; FOUR where the launch does not
     // even fill half the CUs (the stride-2 / transposed convs of the 12^3 and 6^3 levels: 28 ... 112 workgroups whose life is K / 64 serial load -> LDS ->
     // barrier stages, 26 us for K = 1024): 16-bit types only (123 KB of LDS, one workgroup per CU - there is one per CU at most anyway)
-    static const int ks_env = 0;
-    const bool ks2 = a.Kpad % (2 * BK) == 0 && a.Kpad >= 4 * BK && (ks_env ? ks_env == 2 : (long long)grid.x * grid.y <= 512);
-    const bool ks4 = sizeof(T) == 2 && a.Kpad % (4 * BK) == 0 && a.Kpad >= 8 * BK && (ks_env ? ks_env == 4 : (long long)grid.x * grid.y <= 128);
-#define SEG_LAUNCH_CONV(NT)                                                                          \
-    if (ks4) {                                                                                        \
-        if constexpr (sizeof(T) == 2) {                                                               \
-            if (a.scatter) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_igemm_kernel<T, NT, true, 4>), grid, dim3(256), 0, s, a, srep);  \
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_igemm_kernel<T, NT, false, 4>), grid, dim3(256), 0, s, a, srep);     \
-        }                                                                                             \
-    } else if (ks2) {                                                                                 \
-        if (a.scatter) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_igemm_kernel<T, NT, true, 2>), grid, dim3(256), 0, s, a, srep);  \
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_igemm_kernel<T, NT, false, 2>), grid, dim3(256), 0, s, a, srep);     \
-    } else if (a.scatter) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_igemm_kernel<T, NT, true, 1>), grid, dim3(256), 0, s, a, srep);  \
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_igemm_kernel<T, NT, false, 1>), grid, dim3(256), 0, s, a, srep);
-    if (nt == 4) { SEG_LAUNCH_CONV(4) } else if (nt == 2) { SEG_LAUNCH_CONV(2) } else { SEG_LAUNCH_CONV(1) }
-#undef SEG_LAUNCH_CONV
+    const bool ks2 = a.Kpad % (2 * BK) == 0 && a.Kpad >= 4 * BK && (long long)grid.x * grid.y <= 512;
+    const bool ks4 = sizeof(T) == 2 && a.Kpad % (4 * BK) == 0 && a.Kpad >= 8 * BK && (long long)grid.x * grid.y <= 128;
+    by_int<4, 2, 1>(nt, [&](auto n) { by_bool(a.scatter, [&](auto sc) { by_int<4, 2, 1>(ks4 ? 4 : ks2 ? 2 : 1, [&](auto ks) {
+        if constexpr (ks() != 4 || sizeof(T) == 2)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_igemm_kernel<T, n(), sc(), ks()>), grid, dim3(256), 0, s, a, srep);
+    }); }); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -554,19 +545,13 @@ bool launch_conv_stream(const ConvArgs& a, hipStream_t s) {
     if (gx > 1024) gx = 1024;
     if (gx < 1) gx = 1;
     dim3 grid(gx, a.N);
-#define SEG_STREAM(KS, NTL)                                                                                                   \
-    if (ks == KS && ntl == NTL) {                                                                                            \
-        if (a.scatter && a.Cout == 16 && NTL > 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_stream_kernel<T, KS, NTL, 2>), grid, dim3(256), 0, s, a); \
-        else if (a.scatter) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_stream_kernel<T, KS, NTL, 1>), grid, dim3(256), 0, s, a); \
-        else if (a.act_scale) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_stream_kernel<T, KS, NTL, 0, true>), grid, dim3(256), 0, s, a); \
-        else if (a.rq_Q) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_stream_kernel<T, KS, NTL, 0, false, true>), grid, dim3(256), 0, s, a); \
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_stream_kernel<T, KS, NTL, 0>), grid, dim3(256), 0, s, a);               \
-        return true;                                                                                                         \
-    }
-    SEG_STREAM(1, 1) SEG_STREAM(1, 2) SEG_STREAM(1, 4) SEG_STREAM(1, 8) SEG_STREAM(2, 1) SEG_STREAM(2, 2) SEG_STREAM(2, 4)
-    SEG_STREAM(4, 1) SEG_STREAM(4, 2)
-#undef SEG_STREAM
-    return false;
+    // form: SC (0 gather / 1 scatter / 2 scatter with one channel tile), 3 = gather with ACT, 4 = gather with RQ
+    const int form = a.scatter ? (a.Cout == 16 && ntl > 1 ? 2 : 1) : a.act_scale ? 3 : a.rq_Q ? 4 : 0;
+    // the (KS, NTL) pairs that exist, as 10 * KS + NTL; any other pair: false
+    return by_int<11, 12, 14, 18, 21, 22, 24, 41, 42>(10 * ks + ntl, [&](auto p) { by_int<0, 1, 2, 3, 4>(form, [&](auto f) {
+        constexpr int KS = p() / 10, NTL = p() % 10, SC = f() <= 2 ? f() : 0;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_stream_kernel<T, KS, NTL, SC, f() == 3, f() == 4>), grid, dim3(256), 0, s, a);
+    }); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -771,17 +756,16 @@ void launch_conv_igemm(const ConvArgs& a, int dtype, hipStream_t s, int stat_rep
     if (a.rq_Q && !stream_eligible(a)) { fprintf(stderr, "segengine: GroupNorm-backward sums on a conv launch need the streaming kernel with two outputs (internal error)\n"); abort(); }
     if (a.out1 && !stream_eligible(a)) { fprintf(stderr, "segengine: two output tensors need the streaming conv kernel (internal error)\n"); abort(); }
     if (a.act_scale && !stream_eligible(a)) { fprintf(stderr, "segengine: activation on load needs the streaming conv kernel (internal error)\n"); abort(); }
-    if (dtype == DT_F32) { if (!launch_conv_stream<float>(a, s)) conv_dispatch<float>(a, s, srep); }
-    else if (dtype == DT_F16) { if (!launch_conv_stream<f16>(a, s)) conv_dispatch<f16>(a, s, srep); }
-    else { if (!launch_conv_stream<bf16>(a, s)) conv_dispatch<bf16>(a, s, srep); }
+    by_dtype(dtype, [&](auto t) {
+        using T = tag_type<decltype(t)>;
+        if (!launch_conv_stream<T>(a, s)) conv_dispatch<T>(a, s, srep);
+    });
 }
 
 void launch_conv_stem(const StemArgs& a, int dtype, hipStream_t s) {
     const long long M = (long long)a.N * a.D * a.H * a.W;
     dim3 grid(cdiv(M, 256));
-    if (dtype == DT_F32) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_stem_kernel<float>), grid, dim3(256), 0, s, a);
-    else if (dtype == DT_F16) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_stem_kernel<f16>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_stem_kernel<bf16>), grid, dim3(256), 0, s, a);
+    by_dtype(dtype, [&](auto t) { hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_stem_kernel<tag_type<decltype(t)>>), grid, dim3(256), 0, s, a); });
 }
 
 void launch_head_fwd(const HeadArgs& a, int dtype, hipStream_t s) {
@@ -789,31 +773,20 @@ void launch_head_fwd(const HeadArgs& a, int dtype, hipStream_t s) {
     int blocks = cdiv(M, 256);
     if (blocks > 8192) blocks = 8192;
     dim3 grid(blocks);
-    if (dtype == DT_F32) hipLaunchKernelGGL(HIP_KERNEL_NAME(head_fwd_kernel<float>), grid, dim3(256), 0, s, a);
-    else if (dtype == DT_F16) hipLaunchKernelGGL(HIP_KERNEL_NAME(head_fwd_kernel<f16>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(head_fwd_kernel<bf16>), grid, dim3(256), 0, s, a);
-}
-
-template <class T>
-static void head_bwd_dispatch(const HeadBwdArgs& a, dim3 grid, hipStream_t s) {
-#define SEG_HB(NC)                                                                                                       \
-    if (a.din) hipLaunchKernelGGL(HIP_KERNEL_NAME(head_bwd_kernel<T, NC, true>), grid, dim3(256), 0, s, a);               \
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(head_bwd_kernel<T, NC, false>), grid, dim3(256), 0, s, a);
-    if (a.C == 1) { SEG_HB(1) } else if (a.C == 2) { SEG_HB(2) } else if (a.C == 3) { SEG_HB(3) } else if (a.C == 4) { SEG_HB(4) }
-    else if (a.C <= 8) { SEG_HB(8) } else { SEG_HB(16) }
-#undef SEG_HB
+    by_dtype(dtype, [&](auto t) { hipLaunchKernelGGL(HIP_KERNEL_NAME(head_fwd_kernel<tag_type<decltype(t)>>), grid, dim3(256), 0, s, a); });
 }
 
 void launch_head_bwd(const HeadBwdArgs& a, int dtype, hipStream_t s) {
     const int VPB = 256 / (a.Cin / 8);
     int blocks = cdiv(a.V, 2 * VPB);           // per sample; two voxels per thread and trip
-    static const int cap = 1024;      // tuning knob: workgroups per launch
+    constexpr int cap = 1024;         // workgroups per launch
     const int per_n = cap / a.N > 0 ? cap / a.N : 1;
     if (blocks > per_n) blocks = per_n;
     dim3 grid(blocks, a.N);
-    if (dtype == DT_F32) head_bwd_dispatch<float>(a, grid, s);
-    else if (dtype == DT_F16) head_bwd_dispatch<f16>(a, grid, s);
-    else head_bwd_dispatch<bf16>(a, grid, s);
+    const int nc = (a.C >= 1 && a.C <= 4) ? a.C : a.C <= 8 ? 8 : 16;          // classes, padded to a kernel that exists
+    by_dtype(dtype, [&](auto t) { by_bool(a.din != nullptr, [&](auto din) { by_int<1, 2, 3, 4, 8, 16>(nc, [&](auto c) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(head_bwd_kernel<tag_type<decltype(t)>, c(), din()>), grid, dim3(256), 0, s, a);
+    }); }); });
 }
 
 }  // namespace seg

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "dispatch.h"
 
 // waves per SIMD the register allocator must leave room for (second __launch_bounds__ argument); tuning knobs of
 // tools/build_variant.py, the defaults are the measured choice
@@ -346,12 +347,11 @@ void conv3_launch_shape(const Conv3Args& a, hipStream_t s) {
     // LDS weight slab (one 16-channel output tile at a time over the resident halo) for every 16-bit tiling; the f32
     // halo is too large to share the LDS with it
     const bool wl = nt == 1 || sizeof(T) == 2;
-#define SEG_C3(CH, NT, WLV) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3_kernel<T, TD, TH, TW, KD, CH, NT, WLV>), grid, dim3(256), 0, s, a)
-    if (a.Cin == 16) { if (nt == 1) SEG_C3(16, 1, true); else if (wl) SEG_C3(16, 2, true); else SEG_C3(16, 2, false); }
-    else if (nt == 1) SEG_C3(32, 1, true);
-    else if (nt == 2) { if (wl) SEG_C3(32, 2, true); else SEG_C3(32, 2, false); }
-    else { if (wl) SEG_C3(32, 4, true); else SEG_C3(32, 4, false); }
-#undef SEG_C3
+    // CH = 16 only for 16 input channels (and then NT <= 2); NT = 1 always takes the weight slab
+    by_int<16, 32>(a.Cin == 16 ? 16 : 32, [&](auto ch) { by_int<1, 2, 4>(nt, [&](auto n) { by_bool(wl, [&](auto w) {
+        if constexpr (!(ch() == 16 && n() == 4) && (n() != 1 || w()))
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3_kernel<T, TD, TH, TW, KD, ch(), n(), w()>), grid, dim3(256), 0, s, a);
+    }); }); });
 }
 
 // box shape per level: x extent 16 when the row length suits it, else 8x8 tiles (24^3, 6^3 levels)
@@ -375,15 +375,13 @@ void conv3_dispatch(const Conv3Args& a, int ndim, hipStream_t s) {
 // 112 accumulator registers per lane next to 48 prefetch registers, which left no room to pipeline the LDS reads (every variant of the pipelined
 // sweep spilled: the compiler's reloads sat between the prefetch loads and serialised them); 32 x 16 needs 56, reads its B fragments a whole K
 // step ahead, writes partial tiles half the size (the reduce pass re-reads half as much) and its 44 KB of LDS / 184 registers leave a halo-conv
-// workgroup of the main stream room on the same CU.  SEG_W3_CQ=32 restores the wide tile.
+// workgroup of the main stream room on the same CU.
 // The 2-D nets keep the wide tile (9 taps: 36 accumulator registers per 16 x 16 sub-tile set, the pressure argument does not apply, and
 // C2 VNet2d 16 x 512^2 measures 6.45 ms per step with it against 6.66 with the narrow one; C4 / C5, 3-D: 4.43 / 4.45 against 4.56 / 4.68,
 // profiles/r04_configs_tile_ab.log).
 inline void wgrad3_tile(int P, int Q, int esz, int ndim, int* CP, int* CQ) {
-    static const int cq = 0;          // 0: by dimensionality
-    const int want = cq ? cq : (ndim == 3 ? 16 : 32);
     *CP = P >= 32 ? 32 : 16;
-    *CQ = (Q >= 32 && (want >= 32 || esz == 4)) ? 32 : 16;
+    *CQ = (Q >= 32 && (ndim != 3 || esz == 4)) ? 32 : 16;
 }
 
 struct Wgrad3Args {
@@ -754,12 +752,9 @@ Wgrad3Reduce wgrad3_launch_shape(const Wgrad3Args& a0, float* dw, long long sP, 
     wgrad3_tile(a.P, a.Q, (int)sizeof(T), KD == 3 ? 3 : 2, &CP, &CQ);
     const int combos = (a.P / CP) * (a.Q / CQ);
     dim3 grid(a.nb, combos);
-#define SEG_W3(CPv, CQv) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3_kernel<T, TD, TH, TW, KD, CPv, CQv>), grid, dim3(256), 0, s, a)
-    if (CP == 32 && CQ == 32) SEG_W3(32, 32);
-    else if (CP == 32) SEG_W3(32, 16);
-    else if (CQ == 32) SEG_W3(16, 32);
-    else SEG_W3(16, 16);
-#undef SEG_W3
+    by_int<32, 16>(CP, [&](auto cp) { by_int<32, 16>(CQ, [&](auto cq) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3_kernel<T, TD, TH, TW, KD, cp(), cq()>), grid, dim3(256), 0, s, a);
+    }); });
     return wgrad3_reduce_desc(a.partial, dw, a.P, a.Q, CP, CQ, KD * 9, a.nb, sP, sQ, qreal);
 }
 
@@ -767,8 +762,11 @@ Wgrad3Reduce wgrad3_launch_shape(const Wgrad3Args& a0, float* dw, long long sP, 
 // profiles/r03_rocprofv3_kernel_stats.txt): a 4 x 8 x 16 box.  The kernel is latency-bound (one box in flight per workgroup), so what counts is
 // bytes per round trip and barriers per voxel: 50 KB instead of 23 KB per trip, 2.7x fewer barrier pairs per voxel, and the halo re-read of x
 // drops from 2.8x to 2.1x (PMC round 3: 349 MB fetched for 226 MB algorithmic).  50.5 KB of LDS; 16-bit tensors only (an f32 box would need 127 KB).
-template <class T> struct Wgrad3Big16 {
-    static bool launch(const Wgrad3Args& a0, float* dw, long long sP, long long sQ, hipStream_t s, int qreal, Wgrad3Reduce* rd) {
+template <class T>
+bool wgrad3_big16(const Wgrad3Args& a0, float* dw, long long sP, long long sQ, hipStream_t s, int qreal, Wgrad3Reduce* rd) {
+    if constexpr (sizeof(T) != 2) {
+        return false;
+    } else {
         const char* env = knob_s("SEG_W3_BOX16");          // 0: off; 1 (default): where the volume holds enough boxes; 2: wherever the shape fits (tests)
         const int on = env ? atoi(env) : 1;
         int CP, CQ;
@@ -785,15 +783,12 @@ template <class T> struct Wgrad3Big16 {
         *rd = wgrad3_reduce_desc(a.partial, dw, a.P, a.Q, 16, 16, 27, a.nb, sP, sQ, qreal);
         return true;
     }
-};
-template <> struct Wgrad3Big16<float> {
-    static bool launch(const Wgrad3Args&, float*, long long, long long, hipStream_t, int, Wgrad3Reduce*) { return false; }
-};
+}
 
 template <class T>
 Wgrad3Reduce wgrad3_dispatch(const Wgrad3Args& a, int ndim, float* dw, long long sP, long long sQ, hipStream_t s, int qreal) {
     Wgrad3Reduce rd;
-    if (ndim == 3 && Wgrad3Big16<T>::launch(a, dw, sP, sQ, s, qreal, &rd)) return rd;
+    if (ndim == 3 && wgrad3_big16<T>(a, dw, sP, sQ, s, qreal, &rd)) return rd;
     if (ndim == 3) return wide_box(a.W) ? wgrad3_launch_shape<T, 3, 4, 16, 3>(a, dw, sP, sQ, s, qreal) : wgrad3_launch_shape<T, 3, 8, 8, 3>(a, dw, sP, sQ, s, qreal);
     return wide_box(a.W) ? wgrad3_launch_shape<T, 1, 8, 16, 1>(a, dw, sP, sQ, s, qreal) : wgrad3_launch_shape<T, 1, 8, 8, 1>(a, dw, sP, sQ, s, qreal);
 }
@@ -1008,46 +1003,9 @@ void launch_conv3(const void* in, const void* w, const float* bias, void* out, d
     a.in = in; a.w = w; a.bias = bias; a.out = out; a.stats = stats;
     a.N = N; a.D = D; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
     a.Kpad = ((ndim == 3 ? 27 : 9) * Cin + 31) / 32 * 32;
-    static const int dbg = 0;
-    a.dbg = dbg;
+    a.dbg = 0;
     a.trace = nullptr;
-    // diagnostics (tools/bench_conv3.py): per-workgroup phase timeline of one launch, printed to stderr
-    static const int trace_on = 0;
-    static unsigned long long* tbuf = nullptr;
-    const size_t tmax = 1 << 18;
-    if (trace_on) {
-        if (!tbuf) (void)hipMalloc(&tbuf, tmax * 6 * sizeof(unsigned long long));
-        (void)hipMemsetAsync(tbuf, 0, tmax * 6 * sizeof(unsigned long long), s);
-        a.trace = tbuf;
-    }
-    if (dtype == DT_F32) conv3_dispatch<float>(a, ndim, s);
-    else if (dtype == DT_F16) conv3_dispatch<f16>(a, ndim, s);
-    else conv3_dispatch<bf16>(a, ndim, s);
-    if (trace_on) {
-        (void)hipStreamSynchronize(s);
-        std::vector<unsigned long long> h(tmax * 6);
-        (void)hipMemcpy(h.data(), tbuf, h.size() * 8, hipMemcpyDeviceToHost);
-        size_t n = 0;
-        unsigned long long t0 = ~0ull, t1 = 0;
-        double ph[5] = {0, 0, 0, 0, 0};
-        for (size_t i = 0; i < tmax; ++i) {
-            const unsigned long long* r = &h[i * 6];
-            if (!r[0] || !r[5]) continue;
-            ++n;
-            if (r[0] < t0) t0 = r[0];
-            if (r[5] > t1) t1 = r[5];
-            for (int k = 0; k < 5; ++k) ph[k] += (double)(r[k + 1] - r[k]);
-        }
-        if (n) {
-            // start-time histogram in 10 buckets over the kernel span -> how many "rounds" of workgroups there are
-            int hist[10] = {0};
-            for (size_t i = 0; i < tmax; ++i) if (h[i * 6] && h[i * 6 + 5]) hist[(int)((h[i * 6] - t0) * 10 / (t1 - t0 + 1))]++;
-            fprintf(stderr, "[conv3 trace] C%d->%d %dx%dx%d wgs=%zu span=%.1fus  mean/wg(us): stage=%.2f sync=%.2f loop=%.2f sync=%.2f epilogue=%.2f  starts:",
-                    Cin, Cout, D, H, W, n, (t1 - t0) * 0.01, ph[0] / n * 0.01, ph[1] / n * 0.01, ph[2] / n * 0.01, ph[3] / n * 0.01, ph[4] / n * 0.01);
-            for (int k = 0; k < 10; ++k) fprintf(stderr, " %d", hist[k]);
-            fprintf(stderr, "\n");
-        }
-    }
+    by_dtype(dtype, [&](auto t) { conv3_dispatch<tag_type<decltype(t)>>(a, ndim, s); });
 }
 
 int wgrad3_blocks_per_combo(int ndim, int N, int D, int H, int W, int P, int Q, int esz) {
@@ -1063,7 +1021,7 @@ int wgrad3_blocks_per_combo(int ndim, int N, int D, int H, int W, int P, int Q, 
 #ifdef SEG_DIAG
     static const int total_env = knob_i("SEG_W3_TOTAL", 0), minbox = knob_i("SEG_W3_MINBOX", 6);      // diagnostic variant builds only (tools/build_variant.py)
 #else
-    static const int total_env = 0, minbox = 6;
+    constexpr int total_env = 0, minbox = 6;
 #endif
     const int total = total_env > 0 ? total_env : (ndim == 3 ? 256 : 512);
     // 16 -> 16 channels (the finest level): four workgroups fit a CU (23 KB LDS, 113 VGPRs) and the partial tile is 27 KB, so the
@@ -1071,7 +1029,7 @@ int wgrad3_blocks_per_combo(int ndim, int N, int D, int H, int W, int P, int Q, 
     // round 2 (no prefetch), standalone 4x96^3: 512 -> 168 us, 1024 -> 123 us, 2048 -> 137 us (r02_wgrad16_ab.log), step unchanged.  With the
     // prefetching kernel inside the step (profiles/r03_wgrad_policy_ab3.log): 128 -> 947, 256 -> 967 / 967, 384 -> 961, 1024 -> 956-958
     // volumes/s - one workgroup per CU leaves the bandwidth-bound 96^3 GroupNorm passes of the main stream the rest of the machine
-    static const int total16 = 256;
+    constexpr int total16 = 256;
     long long nb = (P == 16 && Q == 16 ? total16 : total) / combos;
     if (nb < 1) nb = 1;
     const long long nbox = boxes_for(ndim, N, D, H, W);
@@ -1126,9 +1084,8 @@ void launch_wgrad3(const void* dr, const void* x, float* partial, float* dw, int
     (void)hipMemsetAsync(tbuf, 0, tmax * 8 * sizeof(unsigned long long), s);
     a.trace = tbuf;
 #endif
-    const Wgrad3Reduce rd = dtype == DT_F32 ? wgrad3_dispatch<float>(a, ndim, dw, (long long)qreal * T, T, s, qreal)
-                            : dtype == DT_F16 ? wgrad3_dispatch<f16>(a, ndim, dw, (long long)qreal * T, T, s, qreal)
-                                              : wgrad3_dispatch<bf16>(a, ndim, dw, (long long)qreal * T, T, s, qreal);
+    Wgrad3Reduce rd;
+    by_dtype(dtype, [&](auto t) { rd = wgrad3_dispatch<tag_type<decltype(t)>>(a, ndim, dw, (long long)qreal * T, T, s, qreal); });
     if (defer) *defer = rd;                      // the caller batches the reduce (launch_wgrad3_reduce) behind further weight-gradient kernels
     else launch_wgrad3_reduce(&rd, 1, s);
 #ifdef SEG_W3_TRACE
@@ -1167,9 +1124,7 @@ void launch_stem_fwd(const void* in, const void* w, const float* bias, void* out
     StemMArgs a{};
     a.in = in; a.w = w; a.bias = bias; a.out = out; a.stats = stats;
     a.N = N; a.D = D; a.H = H; a.W = W; a.Cimg = Cimg; a.Cout = Cout; a.center = center;
-    if (dtype == DT_F32) stem_dispatch<float>(a, ndim, false, nullptr, s);
-    else if (dtype == DT_F16) stem_dispatch<f16>(a, ndim, false, nullptr, s);
-    else stem_dispatch<bf16>(a, ndim, false, nullptr, s);
+    by_dtype(dtype, [&](auto t) { stem_dispatch<tag_type<decltype(t)>>(a, ndim, false, nullptr, s); });
 }
 void launch_stem_wgrad(const void* dr, const void* in, float* partial, float* dw, int N, int D, int H, int W, int Cimg, int Cout,
                        int center, int ndim, int dtype, hipStream_t s) {
@@ -1177,8 +1132,6 @@ void launch_stem_wgrad(const void* dr, const void* in, float* partial, float* dw
     a.dr = dr; a.in = in; a.partial = partial;
     a.N = N; a.D = D; a.H = H; a.W = W; a.Cimg = Cimg; a.Cout = Cout; a.center = center;
     a.nb = stem_wgrad_blocks(ndim, N, D, H, W);
-    if (dtype == DT_F32) stem_dispatch<float>(a, ndim, true, dw, s);
-    else if (dtype == DT_F16) stem_dispatch<f16>(a, ndim, true, dw, s);
-    else stem_dispatch<bf16>(a, ndim, true, dw, s);
+    by_dtype(dtype, [&](auto t) { stem_dispatch<tag_type<decltype(t)>>(a, ndim, true, dw, s); });
 }
 }  // namespace seg

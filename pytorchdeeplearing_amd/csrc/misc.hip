@@ -3,6 +3,7 @@
 // Adam/AdamW (torch.optim semantics, model/modelVNet.py:548, model/modelUnet.py:849) and the
 // channel-dropout multiplier generator.
 #include "kernels.h"
+#include "dispatch.h"
 
 namespace seg {
 namespace {
@@ -731,14 +732,17 @@ void launch_ingest(const float* x, void* out, int N, int C, long long V, int dty
     if (C == 1 && Csrc == 1 && dtype != DT_F32 && ((long long)N * V) % 8 == 0 && (((unsigned long long)x | (unsigned long long)out) & 15) == 0) {
         const long long total8 = (long long)N * V / 8;
         dim3 g1(ew_blocks(total8));
-        if (dtype == DT_F16) hipLaunchKernelGGL(HIP_KERNEL_NAME(ingest1_kernel<f16>), g1, dim3(256), 0, s, x, (f16*)out, total8, rd);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(ingest1_kernel<bf16>), g1, dim3(256), 0, s, x, (bf16*)out, total8, rd);
+        by_dtype(dtype, [&](auto t) {
+            using T = tag_type<decltype(t)>;
+            if constexpr (sizeof(T) == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(ingest1_kernel<T>), g1, dim3(256), 0, s, x, (T*)out, total8, rd);
+        });
         return;
     }
     dim3 grid(ew_blocks((long long)N * V * C));
-    if (dtype == DT_F32) hipLaunchKernelGGL(HIP_KERNEL_NAME(ingest_kernel<float>), grid, dim3(256), 0, s, x, (float*)out, N, C, V, Csrc, rd);
-    else if (dtype == DT_F16) hipLaunchKernelGGL(HIP_KERNEL_NAME(ingest_kernel<f16>), grid, dim3(256), 0, s, x, (f16*)out, N, C, V, Csrc, rd);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(ingest_kernel<bf16>), grid, dim3(256), 0, s, x, (bf16*)out, N, C, V, Csrc, rd);
+    by_dtype(dtype, [&](auto t) {
+        using T = tag_type<decltype(t)>;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(ingest_kernel<T>), grid, dim3(256), 0, s, x, (T*)out, N, C, V, Csrc, rd);
+    });
 }
 
 // predict() post-processing on the device (modelVNet.py:670-676, modelUnet.py:672-680): probs planar fp32 [N][C][V] ->
@@ -770,24 +774,18 @@ void launch_pack(const PackDesc* descs_dev, int ndesc, int max_elems, int dtype,
     (void)max_elems;
     // rows are strided over `wgs` workgroups per descriptor.  The 256-channel levels hold most of the bytes in descriptors of 256
     // rows: at 64 workgroups each one walked four 27 KB rows back to back (67 us per step, latency-bound)
-    static const int wgs = 256;
+    constexpr int wgs = 256;
     dim3 grid(wgs, ndesc);
-    if (dtype == DT_F32) hipLaunchKernelGGL(HIP_KERNEL_NAME(pack_kernel<float>), grid, dim3(256), 0, s, descs_dev, rd);
-    else if (dtype == DT_F16) hipLaunchKernelGGL(HIP_KERNEL_NAME(pack_kernel<f16>), grid, dim3(256), 0, s, descs_dev, rd);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(pack_kernel<bf16>), grid, dim3(256), 0, s, descs_dev, rd);
+    by_dtype(dtype, [&](auto t) { hipLaunchKernelGGL(HIP_KERNEL_NAME(pack_kernel<tag_type<decltype(t)>>), grid, dim3(256), 0, s, descs_dev, rd); });
 }
 
 void launch_maxpool_fwd(const PoolArgs& a, int dtype, hipStream_t s) {
     dim3 grid(ew_blocks((long long)a.N * (a.D / a.pd) * (a.H / a.ph) * (a.W / a.pw) * (a.C / 8)));
-    if (dtype == DT_F32) hipLaunchKernelGGL(HIP_KERNEL_NAME(maxpool_fwd_kernel<float>), grid, dim3(256), 0, s, a);
-    else if (dtype == DT_F16) hipLaunchKernelGGL(HIP_KERNEL_NAME(maxpool_fwd_kernel<f16>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(maxpool_fwd_kernel<bf16>), grid, dim3(256), 0, s, a);
+    by_dtype(dtype, [&](auto t) { hipLaunchKernelGGL(HIP_KERNEL_NAME(maxpool_fwd_kernel<tag_type<decltype(t)>>), grid, dim3(256), 0, s, a); });
 }
 void launch_maxpool_bwd(const PoolArgs& a, int dtype, hipStream_t s) {
     dim3 grid(ew_blocks((long long)a.N * (a.D / a.pd) * (a.H / a.ph) * (a.W / a.pw) * (a.C / 8)));
-    if (dtype == DT_F32) hipLaunchKernelGGL(HIP_KERNEL_NAME(maxpool_bwd_kernel<float>), grid, dim3(256), 0, s, a);
-    else if (dtype == DT_F16) hipLaunchKernelGGL(HIP_KERNEL_NAME(maxpool_bwd_kernel<f16>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(maxpool_bwd_kernel<bf16>), grid, dim3(256), 0, s, a);
+    by_dtype(dtype, [&](auto t) { hipLaunchKernelGGL(HIP_KERNEL_NAME(maxpool_bwd_kernel<tag_type<decltype(t)>>), grid, dim3(256), 0, s, a); });
 }
 
 
@@ -821,9 +819,10 @@ void launch_colsum(const void* x, float* out, long long M, int C, int dtype, hip
     long long rpb = 4096;
     while (cdiv(M, rpb) > 512) rpb *= 2;
     dim3 grid(cdiv(M, rpb));
-    if (dtype == DT_F32) hipLaunchKernelGGL(HIP_KERNEL_NAME(colsum_kernel<float>), grid, dim3(256), 0, s, (const float*)x, out, M, C, rpb);
-    else if (dtype == DT_F16) hipLaunchKernelGGL(HIP_KERNEL_NAME(colsum_kernel<f16>), grid, dim3(256), 0, s, (const f16*)x, out, M, C, rpb);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(colsum_kernel<bf16>), grid, dim3(256), 0, s, (const bf16*)x, out, M, C, rpb);
+    by_dtype(dtype, [&](auto t) {
+        using T = tag_type<decltype(t)>;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(colsum_kernel<T>), grid, dim3(256), 0, s, (const T*)x, out, M, C, rpb);
+    });
 }
 
 void launch_grad_check(const float* g, long long n, int* found_inf, hipStream_t s) {

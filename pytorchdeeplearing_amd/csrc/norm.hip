@@ -8,6 +8,7 @@
 #include <cstdlib>
 
 #include "kernels.h"
+#include "dispatch.h"
 #include "gn_fold.h"
 
 namespace seg {
@@ -915,25 +916,20 @@ void launch_gn_act(const ActArgs& a, int dtype, hipStream_t s) {
     int bx = ew_blocks(a.V * (a.C / 8));
     if (a.fold) {
         // every workgroup repeats the fold: fewer, longer-running workgroups on the big levels
-        static const int cap = 2048;
+        constexpr int cap = 2048;
         const int per_n = cap / a.N > 0 ? cap / a.N : 1;
         if (bx > per_n) bx = per_n;
     }
     dim3 grid(bx, a.N);
-#define SEG_ACT2(T_, R2_, RS_) { if (a.fold) hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_act_kernel<T_, true, R2_, RS_>), grid, dim3(256), 0, s, a); \
-                                 else hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_act_kernel<T_, false, R2_, RS_>), grid, dim3(256), 0, s, a); }
-#define SEG_ACTH(T_, RS_, HC_) { if (a.fold) hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_act_kernel<T_, true, false, RS_, HC_>), grid, dim3(256), 0, s, a); \
-                                 else hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_act_kernel<T_, false, false, RS_, HC_>), grid, dim3(256), 0, s, a); }
-#define SEG_ACT(T_) { if (a.head_w && a.head_C == 1) { if (a.res) SEG_ACTH(T_, true, 1) else SEG_ACTH(T_, false, 1) }             \
-                      else if (a.head_w && a.head_C == 2) { if (a.res) SEG_ACTH(T_, true, 2) else SEG_ACTH(T_, false, 2) }        \
-                      else if (a.head_w) { if (a.res) SEG_ACTH(T_, true, 4) else SEG_ACTH(T_, false, 4) }                         \
-                      else if (a.r2 && a.res) SEG_ACT2(T_, true, true) else if (a.r2) SEG_ACT2(T_, true, false) \
-                      else if (a.res) SEG_ACT2(T_, false, true) else SEG_ACT2(T_, false, false) }
     if (a.head_w && !gn_act_head_supported(a.C, a.head_C, a.r2 != nullptr)) { fprintf(stderr, "segengine: head in the activation pass: unsupported shape (internal error)\n"); abort(); }
-    if (dtype == DT_F32) SEG_ACT(float) else if (dtype == DT_F16) SEG_ACT(f16) else SEG_ACT(bf16)
-#undef SEG_ACT
-#undef SEG_ACTH
-#undef SEG_ACT2
+    // HC: the head's classes computed in this pass (1, 2, else 4), 0 without a head; the head forms exist for one branch (no R2) only
+    const int hc = !a.head_w ? 0 : a.head_C == 1 ? 1 : a.head_C == 2 ? 2 : 4;
+    by_dtype(dtype, [&](auto t) { by_bool(a.fold, [&](auto fold) { by_bool(a.r2 && !hc, [&](auto r2) { by_bool(a.res != nullptr, [&](auto rs) {
+        by_int<0, 1, 2, 4>(hc, [&](auto h) {
+            if constexpr (!(r2() && h()))
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_act_kernel<tag_type<decltype(t)>, fold(), r2(), rs(), h()>), grid, dim3(256), 0, s, a);
+        });
+    }); }); }); });
 }
 
 void launch_gn_bwd_reduce(const GnBwdArgs& a, int dtype, hipStream_t s) {
@@ -943,18 +939,14 @@ void launch_gn_bwd_reduce(const GnBwdArgs& a, int dtype, hipStream_t s) {
     long long rows = ((long long)a.N * a.V + 2047) / 2048;
     rows = (rows + G - 1) / G * G;
     if (rows < 2 * G) rows = 2 * G;
-    static const int max_rows = 1024;   // measured: 256 -> 686, 512 -> 688, 1024..4096 -> 690.5 volumes/s
+    constexpr int max_rows = 1024;   // measured: 256 -> 686, 512 -> 688, 1024..4096 -> 690.5 volumes/s
     if (rows > max_rows) rows = max_rows / G * G;
     const int GNB_ROWS = (int)rows;
     dim3 grid(cdiv(a.V, GNB_ROWS), a.N);
     const int nv = dy_variant(a);
-#define SEG_GNR1(T_, D_, K_) hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_bwd_reduce_kernel<T_, D_, K_>), grid, dim3(256), 0, s, a, GNB_ROWS)
-#define SEG_GNR(T_, D_) { if (nv == 1) SEG_GNR1(T_, D_, 1); else if (nv == 2) SEG_GNR1(T_, D_, 2); else if (nv == 3) SEG_GNR1(T_, D_, 3); \
-                          else if (nv == 4) SEG_GNR1(T_, D_, 4); else if (nv == 5) SEG_GNR1(T_, D_, 5); else SEG_GNR1(T_, D_, 0); }
-    if (a.r2) { if (dtype == DT_F32) SEG_GNR(float, true) else if (dtype == DT_F16) SEG_GNR(f16, true) else SEG_GNR(bf16, true) }
-    else { if (dtype == DT_F32) SEG_GNR(float, false) else if (dtype == DT_F16) SEG_GNR(f16, false) else SEG_GNR(bf16, false) }
-#undef SEG_GNR
-#undef SEG_GNR1
+    by_dtype(dtype, [&](auto t) { by_bool(a.r2 != nullptr, [&](auto dual) { by_int<1, 2, 3, 4, 5, 0>(nv, [&](auto k) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_bwd_reduce_kernel<tag_type<decltype(t)>, dual(), k()>), grid, dim3(256), 0, s, a, GNB_ROWS);
+    }); }); });
 }
 
 // measured on MI355X: one workgroup per (n,g) only wins while the per-sample tensor is <= ~128 KB (the 6^3 level:
@@ -964,17 +956,13 @@ bool gn_bwd_group_eligible(int C, long long V, int esz) { return C >= 64 && C <=
 void launch_gn_fwd_group(const GnFinArgs& f, const void* r, const void* res, void* out, int dtype, hipStream_t s) {
     GnFwdGroupArgs a; a.f = f; a.r = r; a.res = res; a.out = out;
     dim3 grid(GN_GROUPS, f.N);
-    if (dtype == DT_F32) hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_fwd_group_kernel<float>), grid, dim3(1024), 0, s, a);
-    else if (dtype == DT_F16) hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_fwd_group_kernel<f16>), grid, dim3(1024), 0, s, a);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_fwd_group_kernel<bf16>), grid, dim3(1024), 0, s, a);
+    by_dtype(dtype, [&](auto t) { hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_fwd_group_kernel<tag_type<decltype(t)>>), grid, dim3(1024), 0, s, a); });
 }
 
 void launch_gn_bwd_group(const GnBwdArgs& e, const GnBwdFinArgs& f, int dtype, hipStream_t s) {
     GnBwdGroupArgs a; a.e = e; a.f = f;
     dim3 grid(GN_GROUPS, e.N);
-    if (dtype == DT_F32) hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_bwd_group_kernel<float>), grid, dim3(1024), 0, s, a);
-    else if (dtype == DT_F16) hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_bwd_group_kernel<f16>), grid, dim3(1024), 0, s, a);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_bwd_group_kernel<bf16>), grid, dim3(1024), 0, s, a);
+    by_dtype(dtype, [&](auto t) { hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_bwd_group_kernel<tag_type<decltype(t)>>), grid, dim3(1024), 0, s, a); });
 }
 
 // S workgroups of 256 threads per (sample, group), ku <= K chunks per thread: about one workgroup per CU in all, more where a slice would not fit the
@@ -1014,18 +1002,22 @@ void launch_gn_bwd_coop(const GnBwdArgs& e, const GnBwdFinArgs& f, int dtype, hi
     a.slots = (unsigned long long*)e.Q;
     gn_bwd_coop_plan(e.C, e.V, e.N, dtype == DT_F32 ? 4 : 2, &a.S, &a.ku);
     dim3 grid(GN_GROUPS * a.S, e.N);
+    // K: chunks per thread, the smallest of 2 / 4 / 8 that holds ku (8 only for the 16-bit types: the plan keeps ku <= 4 for f32); NDY: 1, 2, else 3
+    const int ndy = e.ndy == 1 ? 1 : e.ndy == 2 ? 2 : 3;
+    by_dtype(dtype, [&](auto t) {
+        using T = tag_type<decltype(t)>;
+        const int kk = a.ku <= 2 ? 2 : (a.ku <= 4 || sizeof(T) != 2) ? 4 : 8;
+        by_int<1, 2, 3>(ndy, [&](auto d) { by_int<2, 4, 8>(kk, [&](auto k) {
+            if constexpr (k() != 8 || sizeof(T) == 2) {
 #ifdef SEG_EMU
-#define SEG_GNC2(T_, D_, K_) { hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_bwd_coop_kernel<T_, D_, K_, 1>), grid, dim3(256), 0, s, a); \
-                               hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_bwd_coop_kernel<T_, D_, K_, 2>), grid, dim3(256), 0, s, a); }
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_bwd_coop_kernel<T, d(), k(), 1>), grid, dim3(256), 0, s, a);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_bwd_coop_kernel<T, d(), k(), 2>), grid, dim3(256), 0, s, a);
 #else
-#define SEG_GNC2(T_, D_, K_) hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_bwd_coop_kernel<T_, D_, K_, 0>), grid, dim3(256), 0, s, a);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_bwd_coop_kernel<T, d(), k(), 0>), grid, dim3(256), 0, s, a);
 #endif
-#define SEG_GNC1(T_, D_) { if (a.ku <= 2) SEG_GNC2(T_, D_, 2) else if (a.ku <= 4) SEG_GNC2(T_, D_, 4) else SEG_GNC2(T_, D_, (sizeof(T_) == 2 ? 8 : 4)) }
-#define SEG_GNC(T_) { if (e.ndy == 1) SEG_GNC1(T_, 1) else if (e.ndy == 2) SEG_GNC1(T_, 2) else SEG_GNC1(T_, 3) }
-    if (dtype == DT_F32) SEG_GNC(float) else if (dtype == DT_F16) SEG_GNC(f16) else SEG_GNC(bf16)
-#undef SEG_GNC
-#undef SEG_GNC1
-#undef SEG_GNC2
+            }
+        }); });
+    });
 }
 
 void launch_gn_bwd_finalize(const GnBwdFinArgs& a, hipStream_t s, const GnBwdFinArgs* b) {
@@ -1037,21 +1029,16 @@ void launch_gn_bwd_apply(const GnBwdArgs& a, int dtype, hipStream_t s, const GnB
     int bx = ew_blocks(a.V * (a.C / 8));
     const bool fold = fa != nullptr;
     if (fold) {
-        static const int cap = 2048;
+        constexpr int cap = 2048;
         const int per_n = cap / a.N > 0 ? cap / a.N : 1;
         if (bx > per_n) bx = per_n;
     }
     dim3 grid(bx, a.N);
     const GnBwdFinArgs za = fa ? *fa : GnBwdFinArgs{}, zb = fb ? *fb : GnBwdFinArgs{};
     const int nv = dy_variant(a);
-#define SEG_GNA1(T_, D_, K_) { if (fold) hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_bwd_apply_kernel<T_, D_, true, K_>), grid, dim3(256), 0, s, a, za, zb); \
-                               else hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_bwd_apply_kernel<T_, D_, false, K_>), grid, dim3(256), 0, s, a, za, zb); }
-#define SEG_GNA(T_, D_) { if (nv == 1) SEG_GNA1(T_, D_, 1) else if (nv == 2) SEG_GNA1(T_, D_, 2) else if (nv == 3) SEG_GNA1(T_, D_, 3) \
-                          else if (nv == 4) SEG_GNA1(T_, D_, 4) else if (nv == 5) SEG_GNA1(T_, D_, 5) else SEG_GNA1(T_, D_, 0) }
-    if (a.r2) { if (dtype == DT_F32) SEG_GNA(float, true) else if (dtype == DT_F16) SEG_GNA(f16, true) else SEG_GNA(bf16, true) }
-    else { if (dtype == DT_F32) SEG_GNA(float, false) else if (dtype == DT_F16) SEG_GNA(f16, false) else SEG_GNA(bf16, false) }
-#undef SEG_GNA
-#undef SEG_GNA1
+    by_dtype(dtype, [&](auto t) { by_bool(a.r2 != nullptr, [&](auto dual) { by_bool(fold, [&](auto fd) { by_int<1, 2, 3, 4, 5, 0>(nv, [&](auto k) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_bwd_apply_kernel<tag_type<decltype(t)>, dual(), fd(), k()>), grid, dim3(256), 0, s, a, za, zb);
+    }); }); }); });
 }
 
 }  // namespace seg

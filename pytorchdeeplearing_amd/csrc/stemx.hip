@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "dispatch.h"
 
 namespace seg {
 namespace {
@@ -429,22 +430,20 @@ __global__ __launch_bounds__(256) void stemx_wgrad_reduce_kernel(const float* pa
 template <class T, class B, int CIMG>
 void launch_mode(const StemxArgs& a, int mode, int nwg, hipStream_t s) {
     dim3 grid(nwg), block(256);
-#define SEG_SXK(M, ND) hipLaunchKernelGGL(HIP_KERNEL_NAME(stemx_kernel<T, B, M, CIMG, ND>), grid, block, 0, s, a)
-    switch (mode) {
-        case SX_FWD_STATS: SEG_SXK(SX_FWD_STATS, 0); break;
-        case SX_FWD_APPLY: SEG_SXK(SX_FWD_APPLY, 0); break;
-        case SX_BWD_REDUCE: if (a.ndy == 1) SEG_SXK(SX_BWD_REDUCE, 1); else if (a.ndy == 2) SEG_SXK(SX_BWD_REDUCE, 2); else SEG_SXK(SX_BWD_REDUCE, 3); break;
-        default: if (a.ndy == 1) SEG_SXK(SX_BWD_APPLY, 1); else if (a.ndy == 2) SEG_SXK(SX_BWD_APPLY, 2); else SEG_SXK(SX_BWD_APPLY, 3); break;
-    }
-#undef SEG_SXK
+    // the forward modes take no gradient sources (NDY = 0), the backward ones 1, 2 or (anything else) 3; any mode past SX_BWD_REDUCE is the backward apply
+    const bool fwd = mode == SX_FWD_STATS || mode == SX_FWD_APPLY;
+    const int m = fwd || mode == SX_BWD_REDUCE ? mode : SX_BWD_APPLY, nd = fwd ? 0 : a.ndy == 1 ? 1 : a.ndy == 2 ? 2 : 3;
+    by_int<SX_FWD_STATS, SX_FWD_APPLY, SX_BWD_REDUCE, SX_BWD_APPLY>(m, [&](auto md) { by_int<0, 1, 2, 3>(nd, [&](auto n) {
+        if constexpr ((md() == SX_FWD_STATS || md() == SX_FWD_APPLY) == (n() == 0))
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(stemx_kernel<T, B, md(), CIMG, n()>), grid, block, 0, s, a);
+    }); });
 }
 
 // the forward apply pass (no gradient-source tiles in LDS, no accumulators) on a box of its own choice
 template <class T, class B, int CIMG>
-void launch_fwd_mode(const StemxArgs& a, int mode, hipStream_t s) {
+void launch_fwd_mode(const StemxArgs& a, hipStream_t s) {
     const long long nb = (long long)a.N * ((a.D + B::TD - 1) / B::TD) * ((a.H + B::TH - 1) / B::TH) * ((a.W + 15) / 16);
     dim3 grid((unsigned)(nb < 2048 ? nb : 2048)), block(256);
-    (void)mode;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(stemx_kernel<T, B, SX_FWD_APPLY, CIMG, 0>), grid, block, 0, s, a);
 }
 
@@ -457,7 +456,7 @@ inline long long sx_boxes(int ndim, int N, int D, int H, int W) {
 
 int stemx_workgroups(int ndim, int N, int D, int H, int W) {
     const long long nb = sx_boxes(ndim, N, ndim == 3 ? D : 1, H, W);
-    static const int cap = 2048;
+    constexpr int cap = 2048;
     return (int)(nb < cap ? nb : cap);
 }
 size_t stemx_partial_bytes(int ndim, int N, int D, int H, int W, int Cimg) {
@@ -472,19 +471,15 @@ void launch_stemx(const seg_stemx_args& a0, int mode, int ndim, int dtype, float
     if (ndim == 3 && mode == SX_FWD_APPLY) {
         // 4 x 8 x 16 boxes for the forward apply pass: 2.1 halo elements staged per voxel instead of 2.8, half the per-box bookkeeping (MI355X, 4 x 96^3: 46 -> 36 us;
         // the statistics pass keeps the small box - its accumulators take 131 + 36 registers on the large one, three workgroups per SIMD instead of six, 45 us either way)
-        if (dtype == DT_F32) launch_fwd_mode<float, SBox<4, 8, 3>, 1>(a, mode, s);
-        else if (dtype == DT_F16) launch_fwd_mode<f16, SBox<4, 8, 3>, 1>(a, mode, s);
-        else launch_fwd_mode<bf16, SBox<4, 8, 3>, 1>(a, mode, s);
+        by_dtype(dtype, [&](auto t) { launch_fwd_mode<tag_type<decltype(t)>, SBox<4, 8, 3>, 1>(a, s); });
         return;
     }
-#define SEG_SX(T) do { if (ndim == 3) launch_mode<T, SBox<2, 8, 3>, 1>(a, mode, nwg, s);                    \
-                       else if (a.Cimg == 1) launch_mode<T, SBox<1, 16, 1>, 1>(a, mode, nwg, s);             \
-                       else if (a.Cimg == 2) launch_mode<T, SBox<1, 16, 1>, 2>(a, mode, nwg, s);             \
-                       else launch_mode<T, SBox<1, 16, 1>, 3>(a, mode, nwg, s); } while (0)
-    if (dtype == DT_F32) SEG_SX(float);
-    else if (dtype == DT_F16) SEG_SX(f16);
-    else SEG_SX(bf16);
-#undef SEG_SX
+    // one box per dimensionality; the 2-D form exists for 1, 2 and (anything else) 3 image channels
+    by_dtype(dtype, [&](auto t) {
+        using T = tag_type<decltype(t)>;
+        if (ndim == 3) launch_mode<T, SBox<2, 8, 3>, 1>(a, mode, nwg, s);
+        else by_int<1, 2, 3>(a.Cimg == 1 ? 1 : a.Cimg == 2 ? 2 : 3, [&](auto c) { launch_mode<T, SBox<1, 16, 1>, c()>(a, mode, nwg, s); });
+    });
     if (mode == SX_BWD_APPLY) {
         const int ntap = ndim == 3 ? 27 : 9, K = ntap * a.Cimg, K1 = a.w1 ? a.Cimg : 0;
         const int per = SX_C * (K + K1);

@@ -10,6 +10,7 @@
 // (deterministic, no same-address atomics).
 // Pinned by autograd of the conv call sites in networks/VNet3d.py / Unet3d.py (reference).
 #include "kernels.h"
+#include "dispatch.h"
 #include <cstdlib>
 
 namespace seg {
@@ -429,8 +430,8 @@ WgPlan make_plan(const WgradArgs& a) {
     pl.ntg = (T + pl.TB - 1) / pl.TB;
     const int bx = pl.ntg * pl.ntile;
     // voxel-axis split: ~2048 workgroups in total, at most 1024 slices and 16 MB of partial tiles
-    static const long long total = 2048;        // tuning knobs
-    static const long long pcap = ((4ll << 20));
+    constexpr long long total = 2048;
+    constexpr long long pcap = 4ll << 20;
     long long parts = total / bx;
     if (parts < 1) parts = 1;
     if (parts > 1024) parts = 1024;
@@ -457,12 +458,12 @@ void wgrad_dispatch(const WgradArgs& a, float* partial, hipStream_t s, int qreal
     bool done = false;
     if constexpr (sizeof(T) == 2) {
         if ((direct_on || a.act_scale) && !a.stem && pl.TB == 1 && pl.direct && pl.ntg == 1 && a.C0 % 8 == 0) {
-#define SEG_WGD(ND, NX, DP) if (!done && pl.TP == 16 * ND && pl.TQ == 16 * NX) {                                                                     \
-                if (a.act_scale) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad_direct_kernel<T, ND, NX, DP, true>), grid, dim3(256), 0, s, a, pl, partial);  \
-                else hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad_direct_kernel<T, ND, NX, DP>), grid, dim3(256), 0, s, a, pl, partial);                   \
-                done = true; }
-            SEG_WGD(1, 2, 4) SEG_WGD(2, 4, 3) SEG_WGD(4, 4, 3) SEG_WGD(1, 1, 4) SEG_WGD(2, 2, 4)
-#undef SEG_WGD
+            // the (NPD, NPX, DEPTH) instantiations that exist, as 100 * NPD + 10 * NPX + DEPTH (three steps in flight for the 64-wide q-tiles, else four);
+            // any other tile: not done
+            const int np = pl.TP % 16 ? 0 : pl.TP / 16, nq = pl.TQ % 16 ? 0 : pl.TQ / 16;
+            done = by_int<124, 243, 443, 114, 224>(100 * np + 10 * nq + (nq == 4 ? 3 : 4), [&](auto k) { by_bool(a.act_scale != nullptr, [&](auto act) {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad_direct_kernel<T, k() / 100, k() / 10 % 10, k() % 10, act()>), grid, dim3(256), 0, s, a, pl, partial);
+            }); });
         }
     }
     if (a.act_scale && !done) { fprintf(stderr, "segengine: activation on load needs the direct weight-gradient kernel (internal error)\n"); abort(); }
@@ -498,9 +499,7 @@ size_t wgrad_partial_bytes(const WgradArgs& a) {
 }
 
 void launch_wgrad(const WgradArgs& a, float* partial, int dtype, hipStream_t s, int qreal) {
-    if (dtype == DT_F32) wgrad_dispatch<float>(a, partial, s, qreal);
-    else if (dtype == DT_F16) wgrad_dispatch<f16>(a, partial, s, qreal);
-    else wgrad_dispatch<bf16>(a, partial, s, qreal);
+    by_dtype(dtype, [&](auto t) { wgrad_dispatch<tag_type<decltype(t)>>(a, partial, s, qreal); });
 }
 
 }  // namespace seg

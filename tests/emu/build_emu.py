@@ -12,7 +12,7 @@ CSRC = os.path.join(ROOT, "pytorchdeeplearing_amd", "csrc")
 OUT = os.path.join(HERE, "_build", "libsegengine_emu.so")
 CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 sys.path.insert(0, ROOT)
-from pytorchdeeplearing_amd.build import SRCS          # noqa: E402  (the product's source list)
+from pytorchdeeplearing_amd.build import HDRS, SRCS          # noqa: E402  (the product's source and header lists)
 
 
 def build(force=False):
@@ -25,8 +25,7 @@ def build(force=False):
 
 def _build(force=False):
     srcs = [os.path.join(CSRC, s) for s in SRCS]
-    deps = srcs + [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "conv3x_impl.h"), os.path.join(CSRC, "gn_fold.h"), os.path.join(CSRC, "engine_internal.h"),
-                   os.path.join(HERE, "hip", "hip_runtime.h"), os.path.join(ROOT, "include", "segengine.h")]
+    deps = srcs + HDRS + [os.path.join(HERE, "hip", "hip_runtime.h")]
     hdr_t = max(os.path.getmtime(d) for d in deps[len(srcs):])
     # per-object freshness (an object compiled BEFORE an edit of its source must not hide behind a newer link step)
     stale = lambda s, o: force or not os.path.exists(o) or os.path.getmtime(o) <= max(os.path.getmtime(s), hdr_t)

@@ -343,7 +343,7 @@ def test_wgrad3_halo_exact(dev, dtype, case):
 @pytest.mark.parametrize("dtype", ["f16", "bf16"])
 @pytest.mark.parametrize("sp,N", [((4, 8, 16), 1), ((9, 11, 32), 2), ((8, 16, 12), 1)])
 def test_wgrad3_big_box_16_channels_exact(dev, dtype, sp, N, monkeypatch):
-    """the 4 x 8 x 16-box instantiation of wgrad3_kernel that serves the 16 -> 16 channel convs of the finest level (Wgrad3Big16, conv3.hip; autograd of
+    """the 4 x 8 x 16-box instantiation of wgrad3_kernel that serves the 16 -> 16 channel convs of the finest level (wgrad3_big16, conv3.hip; autograd of
     networks/VNet3d.py:8 at 96^3): whole boxes, ragged boxes on every axis, the 12-wide row of the deep levels; SEG_W3_BOX16=2 forces it
     onto these small volumes."""
     if dtype == "bf16":

@@ -78,9 +78,35 @@ def audit(src):
     return res
 
 
+def digest(src):
+    """{kernel symbol: "<hash of the instruction stream> <hash of the .amdhsa_kernel block>"}: what has to stay equal when only host code changes.  The
+    stream is normalised (no `;` comments, single spaces, no function index in the local labels: the order of emission changes those and nothing else)."""
+    import hashlib
+    txt = assembly(src)
+    h = lambda lines: hashlib.sha256("\n".join(lines).encode()).hexdigest()[:16]
+    res = {}
+    for m in re.finditer(r"^\s*\.amdhsa_kernel (\S+)\n(.*?)^\s*\.end_amdhsa_kernel", txt, re.M | re.S):
+        name, meta = m.group(1), [" ".join(ln.split()) for ln in m.group(2).split("\n") if ln.strip()]
+        body = re.search(r"^%s:[^\n]*\n(.*?)^\.Lfunc_end\d+:" % re.escape(name), txt, re.M | re.S).group(1)
+        code = []
+        for ln in body.replace(m.group(0), "").split("\n"):          # (the metadata block sits between the last instruction and .Lfunc_end)
+            t = " ".join(ln.split(";", 1)[0].split())
+            t = re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1", re.sub(r"\.(LBB|LJTI|LCPI)\d+_", r".\1_", t))
+            if t:
+                code.append(t)
+        res[name] = "%s %s" % (h(code), h(meta))
+    return res
+
+
 if __name__ == "__main__":
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     only = "--chains-only" in sys.argv
+    if "--digest" in sys.argv:                    # one line per kernel: diff the listing of two trees
+        from pytorchdeeplearing_amd.build import SRCS
+        for src in args or SRCS:
+            for k, v in sorted(digest(src).items()):
+                print(src, v, k)
+        sys.exit(0)
     for src in args or ["norm.hip"]:
         for k, v in sorted(audit(src).items(), key=lambda kv: (-kv[1].get("chains", 0), -kv[1].get("vgprs", 0))):
             if only and not v.get("chains"):
