@@ -10,6 +10,7 @@
 
 #include "kernels.h"
 #include "dispatch.h"
+#include "gn_math.h"
 
 namespace seg {
 
@@ -401,7 +402,7 @@ __global__ __launch_bounds__(256) SEG_STREAM_WAVES(SC == 2 && NTL == 8 ? 3 : 1) 
                 for (int ks = 0; ks < KS; ++ks) {
                     typename Mma<T>::frag v;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = from_f<T>(fmaxf(fmaf(asc[ks][e], to_f(xf[u][ks][e]), ash[ks][e]), 0.f));
+                    for (int e = 0; e < 8; ++e) v[e] = from_f<T>(gn_relu(asc[ks][e], to_f(xf[u][ks][e]), ash[ks][e]));
                     if (afrom0[ks]) xf[u][ks] = v;
                 }
             }
@@ -420,7 +421,7 @@ __global__ __launch_bounds__(256) SEG_STREAM_WAVES(SC == 2 && NTL == 8 ? 3 : 1) 
                     if (RQ) {
                         if (j < NT0) {
                             const float yv = to_f(ry[j < NT0 ? j : 0][r]);
-                            const float d = (fmaf(rsc[j < NT0 ? j : 0][r], yv, rsh[j < NT0 ? j : 0][r]) > 0.f) ? f : 0.f;
+                            const float d = gn_gate(rsc[j < NT0 ? j : 0][r], yv, rsh[j < NT0 ? j : 0][r], f);
                             s1[j][r] += d;
                             s2[j][r] = fmaf(d, yv, s2[j][r]);
                         }

@@ -9,7 +9,7 @@
 
 #include "kernels.h"
 #include "dispatch.h"
-#include "gn_fold.h"
+#include "gn_math.h"
 
 namespace seg {
 namespace {
@@ -19,46 +19,25 @@ namespace {
 // (grid.z = 2: the two branches of the fused input block in one launch)
 __global__ __launch_bounds__(64) void gn_finalize_kernel(GnFinArgs a0, GnFinArgs a1) {
     const GnFinArgs a = blockIdx.z ? a1 : a0;
-    __shared__ double csum[64][2];
     const int g = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
     const int cpg = a.C / GN_GROUPS;                    // 2..32 channels per group
     const int RG = 64 / cpg;                            // replica slices per channel
     const int cl = tid % cpg, rg = tid / cpg, c = g * cpg + cl;
-    double s = 0.0, ss = 0.0;
-    if (rg < RG) {
-        // batches of 8 independent loads: a load -> add loop serialises one L2 round trip per replica (16 for C = 256)
-        const int trips = STAT_REP / RG;
-        for (int j0 = 0; j0 < trips; j0 += 8) {
-            double v0[8], v1[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int rep = rg + (j0 + u) * RG;
-                const double* st = a.stats + (((long long)(rep < STAT_REP ? rep : rg) * a.N + n) * a.C + c) * 2;
-                v0[u] = st[0]; v1[u] = st[1];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (j0 + u < trips) { s += v0[u]; ss += v1[u]; }
-        }
-    }
-    const double ts = wave_sum_d(s), tss = wave_sum_d(ss);
-    const double cnt = (double)cpg * (double)a.V;
-    const double mean = ts / cnt;
-    double var = tss / cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const double rstd = 1.0 / sqrt(var + (double)a.eps);
-    (void)csum;
+    double acc[2] = {0.0, 0.0};
+    if (rg < RG)                                        // batches of 8: 16 replicas per thread for C = 256
+        gn_fold_replicas<8, 2>(rg, RG, STAT_REP, acc, [&](int rep, double* v) {
+            const double* st = a.stats + gn_rep_at(rep, a.N, n, a.C, c);
+            v[0] = st[0]; v[1] = st[1];
+        });
+    double mean, rstd;
+    gn_moments(wave_sum_d(acc[0]), wave_sum_d(acc[1]), (double)cpg * (double)a.V, (double)a.eps, mean, rstd);
     if (tid == 0) {
         a.mean[n * GN_GROUPS + g] = (float)mean;
         a.rstd[n * GN_GROUPS + g] = (float)rstd;
     }
     if (tid < cpg) {
-        // in fp64, rounded once: beta - gamma * mean * rstd cancels where a channel's output is centred near zero, and in fp32 the shift
-        // then carries the rounding of its (much larger) terms into every activation of the channel
         const double mk = a.mask ? (double)a.mask[(long long)n * a.mask_ld + c] : 1.0;
-        const double ga = a.gamma[c], be = a.beta[c];
-        a.scale[(long long)n * a.C + c] = (float)(mk * ga * rstd);
-        a.shift[(long long)n * a.C + c] = (float)(mk * (be - ga * mean * rstd));
+        gn_scale_shift(mk, a.gamma[c], a.beta[c], mean, rstd, a.scale[(long long)n * a.C + c], a.shift[(long long)n * a.C + c]);
     }
 }
 
@@ -133,10 +112,10 @@ __global__ __launch_bounds__(256) void gn_act_kernel(ActArgs a) {
         for (int u = 0; u < UNR; ++u) {
             float y[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) y[j] = fmaxf(fmaf(sc[j], to_f(x[u][j]), sh[j]), 0.f);
+            for (int j = 0; j < 8; ++j) y[j] = gn_relu(sc[j], to_f(x[u][j]), sh[j]);
             if (R2) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) y[j] += fmaxf(fmaf(sc2[j], to_f(x2[u][j]), sh2[j]), 0.f);
+                for (int j = 0; j < 8; ++j) y[j] += gn_relu(sc2[j], to_f(x2[u][j]), sh2[j]);
             }
             if (RES) {
 #pragma unroll
@@ -365,83 +344,19 @@ __global__ __launch_bounds__(64) void gn_bwd_finalize_kernel(GnBwdFinArgs a0, Gn
     if (tid < cpg) {
         mk = a.mask ? (double)a.mask[(long long)n * a.mask_ld + c] : 1.0;
         ga = a.gamma[c];
-        q1 = mk * Q1;                                    // sum dz
-        qx = (mk * Q2 - mu * q1) * rs;                   // sum dz * xhat
+        gn_bwd_terms(mk, Q1, Q2, mu, rs, q1, qx);
         atomicAdd(&a.dbeta[c], (float)q1);
         atomicAdd(&a.dgamma[c], (float)qx);
     }
     const double S1 = wave_sum_d(tid < cpg ? ga * q1 : 0.0);
     const double S2 = wave_sum_d(tid < cpg ? ga * qx : 0.0);
     if (tid < cpg) {
-        const double Mg = (double)cpg * (double)a.V;
-        const double A = rs * ga * mk;
-        const double B = -rs * rs * S2 / Mg;
-        const double Cc = -rs * S1 / Mg + rs * rs * S2 * mu / Mg;
+        double A, B, Cc;
+        gn_bwd_coefs(rs, ga, mk, mu, S1, S2, (double)cpg * (double)a.V, A, B, Cc);
         float* co = a.coef + ((long long)n * a.C + c) * 3;
         co[0] = (float)A; co[1] = (float)B; co[2] = (float)Cc;
-        // sum_v dr = A*sum(dzr) + B*sum(r) + Cc*V   (sum(r) from the forward statistics)
-        if (a.dbias) atomicAdd(&a.dbias[c], (float)(A * Q1 + B * R1 + Cc * (double)a.V));
+        if (a.dbias) atomicAdd(&a.dbias[c], (float)gn_bwd_dbias(A, B, Cc, Q1, R1, (double)a.V));
     }
-}
-
-// The backward finalize of one sample inside a consumer workgroup (same decomposition as gn_fold_block): folds the replica
-// partials of Q (sum dz, sum dz*r) and of the forward channel sums, and leaves the A / B / Cc coefficients of every channel in
-// LDS (same formulas as gn_bwd_finalize_kernel).  `publish`: this workgroup adds the gamma / beta / conv-bias gradients of its
-// sample.  Ends with a barrier.
-__device__ __forceinline__ void gn_bwd_fold_block(const GnBwdFinArgs& f, int n, bool publish, double (*part)[3], float* A_s, float* B_s,
-                                                  float* C_s) {
-    const int tid = threadIdx.x, C = f.C, cpg = C / GN_GROUPS;
-    const int S = 256 / C;
-    const int c = tid % C, sl = tid / C;
-    const int nq = f.rep_q > 0 ? f.rep_q : STAT_REP, ns = f.rep_s > 0 ? f.rep_s : STAT_REP;
-    const int nrep = nq > ns ? nq : ns;
-    // loads that do not depend on the folded sums are issued up front (one L2 round trip for the prologue, not two)
-    double mu = 0.0, rs = 0.0, mk = 1.0, ga = 0.0;
-    if (tid < C) {
-        mu = f.mean[n * GN_GROUPS + tid / cpg]; rs = f.rstd[n * GN_GROUPS + tid / cpg];
-        mk = f.mask ? (double)f.mask[(long long)n * f.mask_ld + tid] : 1.0;
-        ga = f.gamma[tid];
-    }
-    double f1 = 0.0, f2 = 0.0, f3 = 0.0;
-    for (int r0 = sl; r0 < nrep; r0 += 4 * S) {
-        double v1[4], v2[4], v3[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int rep = r0 + u * S;
-            const long long o = (((long long)(rep < nrep ? rep : sl) * f.N + n) * C + c) * 2;
-            v1[u] = f.Q[o]; v2[u] = f.Q[o + 1]; v3[u] = f.stats[o];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if (r0 + u * S < nrep) { f1 += v1[u]; f2 += v2[u]; f3 += v3[u]; }
-    }
-    part[tid][0] = f1; part[tid][1] = f2; part[tid][2] = f3;
-    __syncthreads();
-    double Q1 = 0.0, Q2 = 0.0, R1 = 0.0, q1 = 0.0, qx = 0.0;
-    if (tid < C) {
-        for (int k = 0; k < S; ++k) { Q1 += part[tid + k * C][0]; Q2 += part[tid + k * C][1]; R1 += part[tid + k * C][2]; }
-        q1 = mk * Q1;                                    // sum dz
-        qx = (mk * Q2 - mu * q1) * rs;                   // sum dz * xhat
-        if (publish) {
-            atomicAdd(&f.dbeta[c], (float)q1);
-            atomicAdd(&f.dgamma[c], (float)qx);
-        }
-    }
-    double S1 = ga * q1, S2 = ga * qx;
-    for (int o = cpg >> 1; o >= 1; o >>= 1) { S1 += __shfl_xor(S1, o); S2 += __shfl_xor(S2, o); }
-    if (tid < C) {
-        const double Mg = (double)cpg * (double)f.V;
-        const double A = rs * ga * mk;
-        const double B = -rs * rs * S2 / Mg;
-        const double Cc = -rs * S1 / Mg + rs * rs * S2 * mu / Mg;
-        A_s[c] = (float)A; B_s[c] = (float)B; C_s[c] = (float)Cc;
-        if (publish) {
-            if (f.coef) { float* co = f.coef + ((long long)n * C + c) * 3; co[0] = (float)A; co[1] = (float)B; co[2] = (float)Cc; }
-            // sum_v dr = A*sum(dzr) + B*sum(r) + Cc*V   (sum(r) from the forward statistics)
-            if (f.dbias) atomicAdd(&f.dbias[c], (float)(A * Q1 + B * R1 + Cc * (double)f.V));
-        }
-    }
-    __syncthreads();
 }
 
 // FOLD: the backward finalize runs as a per-workgroup prologue (gn_bwd_fold_block); fa / fb are the finalize arguments of the branches
@@ -568,14 +483,7 @@ __global__ __launch_bounds__(1024) void gn_bwd_group_kernel(GnBwdGroupArgs a) {
         const long long i = ((long long)n * V + it / CG) * CPR + g * CG + cg;
         float dy[8];
         load_dy_sum<T>(a.e, i, dy);
-        const vec<T, 8> x = load8(r + i * 8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float xv = to_f(x[j]);
-            const float d = (fmaf(sc[j], xv, sh[j]) > 0.f) ? dy[j] : 0.f;
-            q1[j] += d;
-            q2[j] = fmaf(d, xv, q2[j]);
-        }
+        gn_bwd_accum8(sc, sh, load8(r + i * 8), dy, true, q1, q2);
     }
     // lanes with equal (lane % CG) hold the same channels: butterfly over the remaining lane bits
 #pragma unroll
@@ -587,19 +495,7 @@ __global__ __launch_bounds__(1024) void gn_bwd_group_kernel(GnBwdGroupArgs a) {
         for (int j = 0; j < 8; ++j) { wsum[wv][lane][j] = q1[j]; wsum[wv][lane][8 + j] = q2[j]; }
     }
     // forward sum(r) of the group's channels (bias gradient): fold the statistic replicas
-    if (tid < cpg) {
-        const int nrep = a.f.rep_s > 0 ? a.f.rep_s : STAT_REP;       // the replicas the forward producer wrote
-        double r1 = 0.0;
-        for (int rep = 0; rep < nrep; rep += 4) {
-            double v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = a.f.stats[(((long long)(rep + u < nrep ? rep + u : 0) * a.f.N + n) * C + g * cpg + tid) * 2];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (rep + u < nrep) r1 += v[u];
-        }
-        chan[tid][2] = r1;
-    }
+    if (tid < cpg) chan[tid][2] = gn_fold_sum_r(a.f, n, g * cpg + tid);
     __syncthreads();
     if (tid < cpg) {
         double s1 = 0.0, s2 = 0.0;
@@ -607,23 +503,10 @@ __global__ __launch_bounds__(1024) void gn_bwd_group_kernel(GnBwdGroupArgs a) {
         chan[tid][0] = s1; chan[tid][1] = s2;
     }
     __syncthreads();
-    if (wv == 0) {                                       // one wave finishes the group: cpg <= 32 channels
-        const int c = g * cpg + (lane < cpg ? lane : 0);
-        const bool act = lane < cpg;
-        const double mu = a.f.mean[n * GN_GROUPS + g], rs = a.f.rstd[n * GN_GROUPS + g];
-        const double mk = act ? (a.f.mask ? (double)a.f.mask[(long long)n * a.f.mask_ld + c] : 1.0) : 0.0;
-        const double ga = act ? (double)a.f.gamma[c] : 0.0;
-        const double Q1 = act ? chan[lane][0] : 0.0, Q2 = act ? chan[lane][1] : 0.0, R1 = act ? chan[lane][2] : 0.0;
-        const double q1d = mk * Q1, qx = (mk * Q2 - mu * q1d) * rs;
-        const double S1 = wave_sum_d(ga * q1d), S2 = wave_sum_d(ga * qx);
-        if (act) {
-            atomicAdd(&a.f.dbeta[c], (float)q1d);
-            atomicAdd(&a.f.dgamma[c], (float)qx);
-            const double Mg = (double)cpg * (double)V;
-            const double A = rs * ga * mk, B = -rs * rs * S2 / Mg, Cc = -rs * S1 / Mg + rs * rs * S2 * mu / Mg;
-            coef[lane][0] = (float)A; coef[lane][1] = (float)B; coef[lane][2] = (float)Cc;
-            if (a.f.dbias) atomicAdd(&a.f.dbias[c], (float)(A * Q1 + B * R1 + Cc * (double)V));
-        }
+    if (wv == 0) {
+        double mu, rs, mk, ga;
+        gn_bwd_group_params(a.f, n, g, lane, mu, rs, mk, ga);
+        gn_bwd_group_finish(a.f, g, lane, mu, rs, mk, ga, chan, coef, true);
     }
     __syncthreads();
     float cA[8], cB[8], cC[8];
@@ -633,15 +516,7 @@ __global__ __launch_bounds__(1024) void gn_bwd_group_kernel(GnBwdGroupArgs a) {
         const long long i = ((long long)n * V + it / CG) * CPR + g * CG + cg;
         float dy[8];
         load_dy_sum<T>(a.e, i, dy);
-        const vec<T, 8> x = load8(r + i * 8);
-        vec<T, 8> o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float xv = to_f(x[j]);
-            const float d = (fmaf(sc[j], xv, sh[j]) > 0.f) ? dy[j] : 0.f;
-            o[j] = from_f<T>(fmaf(cA[j], d, fmaf(cB[j], xv, cC[j])));
-        }
-        store8(dr + i * 8, o);
+        store8(dr + i * 8, gn_bwd_apply8(sc, sh, load8(r + i * 8), dy, cA, cB, cC));
     }
 }
 
@@ -661,32 +536,19 @@ __global__ __launch_bounds__(1024) void gn_fwd_group_kernel(GnFwdGroupArgs a) {
         const int RG = 64 / cpg, cl = lane % cpg, rg = lane / cpg, c = g * cpg + cl;
         // only the replicas the producer wrote (f.rep; 4 at this level, not all 32), four independent 16-B loads per trip: the first version walked
         // all 32 replicas with one dependent L2 round trip per trip - 16 of them, ~10 of this kernel's 11 us (round-4 single-queue trace)
-        const int nrep = a.f.rep > 0 ? a.f.rep : STAT_REP;
-        double s = 0.0, ss = 0.0;
+        double acc[2] = {0.0, 0.0};
         if (rg < RG)
-            for (int rep = rg; rep < nrep; rep += 4 * RG) {
-                double v0[4], v1[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int rr = rep + u * RG;
-                    const double* st = a.f.stats + (((long long)(rr < nrep ? rr : rg) * a.f.N + n) * C + c) * 2;
-                    v0[u] = st[0]; v1[u] = st[1];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (rep + u * RG < nrep) { s += v0[u]; ss += v1[u]; }
-            }
-        const double ts = wave_sum_d(s), tss = wave_sum_d(ss);
-        const double cnt = (double)cpg * (double)V;
-        const double mean = ts / cnt;
-        double var = tss / cnt - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const double rstd = 1.0 / sqrt(var + (double)a.f.eps);
+            gn_fold_replicas<4, 2>(rg, RG, a.f.rep > 0 ? a.f.rep : STAT_REP, acc, [&](int rep, double* v) {
+                const double* st = a.f.stats + gn_rep_at(rep, a.f.N, n, C, c);
+                v[0] = st[0]; v[1] = st[1];
+            });
+        double mean, rstd;
+        gn_moments(wave_sum_d(acc[0]), wave_sum_d(acc[1]), (double)cpg * (double)V, (double)a.f.eps, mean, rstd);
         if (lane == 0) { a.f.mean[n * GN_GROUPS + g] = (float)mean; a.f.rstd[n * GN_GROUPS + g] = (float)rstd; }
         if (lane < cpg) {
             const double mk = a.f.mask ? (double)a.f.mask[(long long)n * a.f.mask_ld + c] : 1.0;
-            const double ga = a.f.gamma[c], be = a.f.beta[c];
-            const float sc = (float)(mk * ga * rstd), sh = (float)(mk * (be - ga * mean * rstd));       // fp64, rounded once (see gn_finalize_kernel)
+            float sc, sh;
+            gn_scale_shift(mk, a.f.gamma[c], a.f.beta[c], mean, rstd, sc, sh);
             ssc[lane] = sc; ssh[lane] = sh;
             a.f.scale[(long long)n * C + c] = sc;
             a.f.shift[(long long)n * C + c] = sh;
@@ -706,7 +568,7 @@ __global__ __launch_bounds__(1024) void gn_fwd_group_kernel(GnFwdGroupArgs a) {
         const vec<T, 8> x = load8(r + i * 8);
         float y[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) y[j] = fmaxf(fmaf(sc[j], to_f(x[j]), sh[j]), 0.f);
+        for (int j = 0; j < 8; ++j) y[j] = gn_relu(sc[j], to_f(x[j]), sh[j]);
         if (res) {
             const vec<T, 8> rr = load8(res + i * 8);
 #pragma unroll
@@ -781,27 +643,10 @@ __global__ __launch_bounds__(256, 2) void gn_bwd_coop_kernel(GnBwdCoopArgs a) { 
     }
     // what the coefficient math needs besides the sums travels with the slice (not as a round trip of its own behind the exchange)
     double f_mu = 0.0, f_rs = 0.0, f_mk = 0.0, f_ga = 0.0;
-    if (wv == 0 && PH != 1) {
-        const int c = g * cpg + (lane < cpg ? lane : 0);
-        f_mu = a.f.mean[n * GN_GROUPS + g]; f_rs = a.f.rstd[n * GN_GROUPS + g];
-        if (lane < cpg) {
-            f_mk = a.f.mask ? (double)a.f.mask[(long long)n * a.f.mask_ld + c] : 1.0;
-            f_ga = (double)a.f.gamma[c];
-        }
-    }
+    if (wv == 0 && PH != 1) gn_bwd_group_params(a.f, n, g, lane, f_mu, f_rs, f_mk, f_ga);
     // forward sum(r) of the group's channels (conv-bias gradient): only the publishing workgroup needs it
     double r1 = 0.0;
-    if (sl == 0 && tid < cpg && PH != 1) {
-        const int nrep = a.f.rep_s > 0 ? a.f.rep_s : STAT_REP;
-        for (int rep = 0; rep < nrep; rep += 4) {
-            double v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = a.f.stats[(((long long)(rep + u < nrep ? rep + u : 0) * a.f.N + n) * C + g * cpg + tid) * 2];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (rep + u < nrep) r1 += v[u];
-        }
-    }
+    if (sl == 0 && tid < cpg && PH != 1) r1 = gn_fold_sum_r(a.f, n, g * cpg + tid);
     if (PH != 2) {
         float q1[8], q2[8];
 #pragma unroll
@@ -810,14 +655,7 @@ __global__ __launch_bounds__(256, 2) void gn_bwd_coop_kernel(GnBwdCoopArgs a) { 
         for (int k = 0; k < K; ++k) {
             float dy[8];
             src[k].sum(dy, vw8);
-            const bool ok = (okm >> k) & 1u;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float xv = to_f(x[k][j]);
-                const float d = (ok && fmaf(sc[j], xv, sh[j]) > 0.f) ? dy[j] : 0.f;
-                q1[j] += d;
-                q2[j] = fmaf(d, xv, q2[j]);
-            }
+            gn_bwd_accum8(sc, sh, x[k], dy, (okm >> k) & 1u, q1, q2);
         }
         // lanes with equal (lane % CG) hold the same channels: DPP sums inside the 16-lane rows, the 16 rows of the workgroup meet in LDS
 #pragma unroll
@@ -863,25 +701,7 @@ __global__ __launch_bounds__(256, 2) void gn_bwd_coop_kernel(GnBwdCoopArgs a) { 
         chan[tid][0] = s1; chan[tid][1] = s2; chan[tid][2] = r1;
     }
     __syncthreads();
-    if (wv == 0) {                                       // one wave finishes the group: cpg <= 32 channels (same formulas as gn_bwd_finalize_kernel)
-        const int c = g * cpg + (lane < cpg ? lane : 0);
-        const bool act = lane < cpg;
-        const bool publish = sl == 0;
-        const double mu = f_mu, rs = f_rs, mk = act ? f_mk : 0.0, ga = act ? f_ga : 0.0;
-        const double Q1 = act ? chan[lane][0] : 0.0, Q2 = act ? chan[lane][1] : 0.0, R1 = act ? chan[lane][2] : 0.0;
-        const double q1d = mk * Q1, qx = (mk * Q2 - mu * q1d) * rs;
-        const double S1 = wave_sum_d(ga * q1d), S2 = wave_sum_d(ga * qx);
-        if (act) {
-            const double Mg = (double)cpg * (double)V;
-            const double A = rs * ga * mk, B = -rs * rs * S2 / Mg, Cc = -rs * S1 / Mg + rs * rs * S2 * mu / Mg;
-            coef[lane][0] = (float)A; coef[lane][1] = (float)B; coef[lane][2] = (float)Cc;
-            if (publish) {
-                atomicAdd(&a.f.dbeta[c], (float)q1d);
-                atomicAdd(&a.f.dgamma[c], (float)qx);
-                if (a.f.dbias) atomicAdd(&a.f.dbias[c], (float)(A * Q1 + B * R1 + Cc * (double)V));
-            }
-        }
-    }
+    if (wv == 0) gn_bwd_group_finish(a.f, g, lane, f_mu, f_rs, f_mk, f_ga, chan, coef, sl == 0);
     __syncthreads();
     float cA[8], cB[8], cC[8];
 #pragma unroll
@@ -890,20 +710,22 @@ __global__ __launch_bounds__(256, 2) void gn_bwd_coop_kernel(GnBwdCoopArgs a) { 
     for (int k = 0; k < K; ++k) {
         float dy[8];
         src[k].sum(dy, vw8);
-        vec<T, 8> o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float xv = to_f(x[k][j]);
-            const float d = (fmaf(sc[j], xv, sh[j]) > 0.f) ? dy[j] : 0.f;
-            o[j] = from_f<T>(fmaf(cA[j], d, fmaf(cB[j], xv, cC[j])));
-        }
-        if ((okm >> k) & 1u) store8(dr + (long long)chunk_of(k) * 8, o);
+        if ((okm >> k) & 1u) store8(dr + (long long)chunk_of(k) * 8, gn_bwd_apply8(sc, sh, x[k], dy, cA, cB, cC));
     }
 }
 
 inline int ew_blocks(long long total_threads) {
     long long b = (total_threads + 255) / 256;
     return (int)(b > 16384 ? 16384 : (b < 1 ? 1 : b));
+}
+// grid.x of the elementwise passes, per sample; fold: every workgroup repeats the finalize prologue - fewer, longer-running workgroups on the big
+// levels (at most ~2048 in all)
+inline int ew_blocks_per_sample(long long total_threads, bool fold, int N) {
+    const int bx = ew_blocks(total_threads);
+    if (!fold) return bx;
+    constexpr int cap = 2048;
+    const int per_n = cap / N > 0 ? cap / N : 1;
+    return bx > per_n ? per_n : bx;
 }
 
 }  // namespace
@@ -913,14 +735,7 @@ void launch_gn_finalize(const GnFinArgs& a, hipStream_t s, const GnFinArgs* b) {
 }
 
 void launch_gn_act(const ActArgs& a, int dtype, hipStream_t s) {
-    int bx = ew_blocks(a.V * (a.C / 8));
-    if (a.fold) {
-        // every workgroup repeats the fold: fewer, longer-running workgroups on the big levels
-        constexpr int cap = 2048;
-        const int per_n = cap / a.N > 0 ? cap / a.N : 1;
-        if (bx > per_n) bx = per_n;
-    }
-    dim3 grid(bx, a.N);
+    dim3 grid(ew_blocks_per_sample(a.V * (a.C / 8), a.fold != 0, a.N), a.N);
     if (a.head_w && !gn_act_head_supported(a.C, a.head_C, a.r2 != nullptr)) { fprintf(stderr, "segengine: head in the activation pass: unsupported shape (internal error)\n"); abort(); }
     // HC: the head's classes computed in this pass (1, 2, else 4), 0 without a head; the head forms exist for one branch (no R2) only
     const int hc = !a.head_w ? 0 : a.head_C == 1 ? 1 : a.head_C == 2 ? 2 : 4;
@@ -1026,14 +841,8 @@ void launch_gn_bwd_finalize(const GnBwdFinArgs& a, hipStream_t s, const GnBwdFin
 
 
 void launch_gn_bwd_apply(const GnBwdArgs& a, int dtype, hipStream_t s, const GnBwdFinArgs* fa, const GnBwdFinArgs* fb) {
-    int bx = ew_blocks(a.V * (a.C / 8));
     const bool fold = fa != nullptr;
-    if (fold) {
-        constexpr int cap = 2048;
-        const int per_n = cap / a.N > 0 ? cap / a.N : 1;
-        if (bx > per_n) bx = per_n;
-    }
-    dim3 grid(bx, a.N);
+    dim3 grid(ew_blocks_per_sample(a.V * (a.C / 8), fold, a.N), a.N);
     const GnBwdFinArgs za = fa ? *fa : GnBwdFinArgs{}, zb = fb ? *fb : GnBwdFinArgs{};
     const int nv = dy_variant(a);
     by_dtype(dtype, [&](auto t) { by_bool(a.r2 != nullptr, [&](auto dual) { by_bool(fold, [&](auto fd) { by_int<1, 2, 3, 4, 5, 0>(nv, [&](auto k) {

@@ -18,6 +18,7 @@
 
 #include "kernels.h"
 #include "dispatch.h"
+#include "gn_math.h"
 
 namespace seg {
 namespace {
@@ -297,10 +298,10 @@ __global__ __launch_bounds__(256) void stemx_kernel(StemxArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float ra = to_f(from_f<T>(pa[r] + bw3[r]));
-                    float yv = fmaxf(fmaf(sw3[r], ra, tw3[r]), 0.f);
+                    float yv = gn_relu(sw3[r], ra, tw3[r]);
                     if (nbr == 2) {
                         const float rb = to_f(from_f<T>(pb[r] + bw1[r]));
-                        yv += fmaxf(fmaf(sw1[r], rb, tw1[r]), 0.f);
+                        yv += gn_relu(sw1[r], rb, tw1[r]);
                     }
                     o[r] = from_f<T>(yv);
                 }
@@ -348,8 +349,8 @@ __global__ __launch_bounds__(256) void stemx_kernel(StemxArgs a) {
             float da[4], db[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                da[r] = (fmaf(sc3, ra[r], sh3) > 0.f) ? dy[r] : 0.f;
-                db[r] = (nbr == 2 && fmaf(sc1, rb[r], sh1) > 0.f) ? dy[r] : 0.f;
+                da[r] = gn_gate(sc3, ra[r], sh3, dy[r]);
+                db[r] = gn_gate(sc1, rb[r], sh1, dy[r], nbr == 2);
             }
             if (MODE == SX_BWD_REDUCE) {
 #pragma unroll

@@ -11,6 +11,7 @@
 // Pinned by autograd of the conv call sites in networks/VNet3d.py / Unet3d.py (reference).
 #include "kernels.h"
 #include "dispatch.h"
+#include "gn_math.h"
 #include <cstdlib>
 
 namespace seg {
@@ -354,7 +355,7 @@ __global__ __launch_bounds__(256) void wgrad_direct_kernel(WgradArgs a, WgPlan p
                         const vec<float, 8> sc = *(const vec<float, 8>*)&coef_s[set][0][c], sh = *(const vec<float, 8>*)&coef_s[set][1][c];
                         vec<T, 8> av;
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) av[e] = from_f<T>(fmaxf(fmaf(sc[e], to_f(xv[e]), sh[e]), 0.f));
+                        for (int e = 0; e < 8; ++e) av[e] = from_f<T>(gn_relu(sc[e], to_f(xv[e]), sh[e]));
                         if (xact[u] >= 0) xv = av;
                     }
                     store8(&Xs[xrow[u] * LDW + ((u * 256 + tid) % cpr_q) * 8], ((okq[k] >> (8 + u)) & 1u) ? xv : zero8<T>());

@@ -192,6 +192,84 @@ def test_coop_phase1_exact(dev, dtype, case):
         assert torch.equal(w.sum(2).reshape(N, C, 2) + 0.0, d["Q"])
 
 
+def exact_params(g, C, N):
+    """gamma / beta multiples of 1/4, dropout multipliers 0 / 1 / 2 in a padded mask, per-group integer mean and power-of-two rstd"""
+    gamma, beta = ints((C,), -4, 4, g) / 4, ints((C,), -8, 8, g) / 4
+    mask = torch.full((N, C + PAD), 7.0)
+    mask[:, :C] = ints((N, C), 0, 2, g)
+    mean = ints((N, 8), -3, 3, g)
+    rstd = torch.tensor([0.25, 0.5, 1.0, 2.0])[torch.randint(0, 4, (N, 8), generator=g)]
+    return gamma, beta, mask, mean, rstd
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_paths_agree_exactly(dev, dtype):
+    """Every path computes the same coefficients from the same sums.  Inputs on which every fp64 intermediate of the coefficient formulas is exact (small
+    integers, multiples of 1/4, powers of two; Mg = 2048; N = 1: one addend per parameter gradient): mean / rstd / scale / shift and coef / dgamma / dbeta /
+    dbias equal the formulas evaluated in float64 and rounded to fp32, with tolerance 0, on every path; out and dr are bit-identical across the paths and
+    within the format bounds of the module docstring of the float64 reference."""
+    C, N, V, rep = 64, 1, 256, 4
+    cpg, Mg = C // 8, float(C // 8 * V)
+    assert ops.gn_group_eligible(C, V, dtype) and ops.gn_coop_plan(C, V, N, dtype) is not None
+    g = torch.Generator().manual_seed(77)
+    rep8 = lambda t: t.double().repeat_interleave(cpg, dim=1)
+    grp = lambda t: rep8(t.reshape(N, 8, cpg).sum(2))
+    f32 = lambda t: t.float().double()
+    bits = lambda t: t.cpu().contiguous().view(torch.uint8)
+    r = ints((N, V, C), -4, 4, g).double()
+    rd = dev_t(r, dtype, dev)
+
+    # ---- backward: statistics as given (not those of r), Q computed by the entry from integer data
+    gamma, beta, mask, mean, rstd = exact_params(g, C, N)
+    mk, ga, mu, rs = mask[:, :C].double(), gamma.double()[None, :], rep8(mean), rep8(rstd)
+    scale, shift = mk * ga * rs, mk * (beta.double()[None, :] - ga * mu * rs)
+    dys = [ints((N, V, C), -2, 2, g).double() for _ in range(2)]
+    dz = (dys[0] + dys[1]) * (scale[:, None, :] * r + shift[:, None, :] > 0)
+    Q1, Q2, R1 = dz.sum(1), (dz * r).sum(1), r.sum(1)
+    q1 = mk * Q1
+    qx = (mk * Q2 - mu * q1) * rs
+    S1, S2 = grp(ga * q1), grp(ga * qx)
+    A, B, Cc = rs * ga * mk, -rs * rs * S2 / Mg, -rs * S1 / Mg + rs * rs * S2 * mu / Mg
+    want = {"dbeta": q1.sum(0), "dgamma": qx.sum(0), "dbias": (A * Q1 + B * R1 + Cc * float(V)).sum(0), "coef": torch.stack([A, B, Cc], dim=2)}
+    dr = A[:, None, :] * dz + B[:, None, :] * r + Cc[:, None, :]
+    dr_terms = (A[:, None, :] * dz).abs() + (B[:, None, :] * r).abs() + Cc.abs()[:, None, :]
+    fwd = dict(scale=dev_f(scale, dev), shift=dev_f(shift, dev), mean=dev_f(mean, dev), rstd=dev_f(rstd, dev))
+    stats = dev_f(scatter(channel_sums(r), rep, g, integer=True), dev, torch.float64)
+    first = None
+    for path in ("separate", "fold", "group", "coop"):
+        o = ops.gn_backward([dev_t(x, dtype, dev) for x in dys], rd, fwd, stats, dev_f(gamma, dev), dtype, path, rep, rep, mask=dev_f(mask, dev))
+        for k in ("dbeta", "dgamma", "dbias") + (("coef",) if path in ("separate", "fold") else ()):
+            print("%s %s largest difference %g" % (path, k, float((o[k].cpu().double() - f32(want[k])).abs().max())))
+            assert torch.equal(o[k].cpu().double(), f32(want[k])), (path, k)
+        if path in ("separate", "fold"):
+            assert torch.equal(o["Q"].cpu().sum(0), torch.stack([Q1, Q2], dim=2)), path
+        check("dr", o["dr"].cpu(), dr, UT[dtype] * dr.abs() + 4 * U32 * dr_terms + SUBNORMAL_STEP[dtype])
+        first = first if first is not None else bits(o["dr"])
+        assert torch.equal(bits(o["dr"]), first), path
+
+    # ---- forward: eps = 0 and synthetic channel sums whose group moments are an integer mean and a variance in {1/4, 1, 4, 16}
+    gamma, beta, mask, mean, rstd = exact_params(g, C, N)
+    mk, ga = mask[:, :C].double(), gamma.double()[None, :]
+    var = 1.0 / (rstd.double() * rstd.double())
+    tot = torch.stack([mean.double() * Mg, (var + mean.double() ** 2) * Mg], dim=2)             # [N, 8, 2]: group sums, integers
+    st = ints((N, 8, cpg, 2), -1000, 1000, g).double()
+    st[:, :, cpg - 1] = tot - st[:, :, :cpg - 1].sum(2)
+    stats = dev_f(scatter(st.reshape(N, C, 2), rep, g, integer=True), dev, torch.float64)
+    scale, shift = mk * ga * rep8(rstd), mk * (beta.double()[None, :] - ga * rep8(mean) * rep8(rstd))
+    want = {"mean1": mean, "rstd1": rstd, "scale1": scale, "shift1": shift}
+    out = torch.relu(scale[:, None, :] * r + shift[:, None, :])
+    terms = (scale[:, None, :] * r).abs() + shift.abs()[:, None, :]
+    first = None
+    for path in ("finalize", "fold", "group"):
+        o = ops.gn_forward(rd, stats, dev_f(gamma, dev), dev_f(beta, dev), dtype, path, rep, mask1=dev_f(mask, dev), eps=0.0)
+        for k in want:
+            print("%s %s largest difference %g" % (path, k, float((o[k].cpu().double() - f32(want[k])).abs().max())))
+            assert torch.equal(o[k].cpu().double(), f32(want[k])), (path, k)
+        check("out", o["out"].cpu(), out, UT[dtype] * out.abs() + 4 * U32 * terms + SUBNORMAL_STEP[dtype])
+        first = first if first is not None else bits(o["out"])
+        assert torch.equal(bits(o["out"]), first), path
+
+
 POOL_WINDOWS = [(2, 2, 2), (1, 2, 2), (1, 1, 1)]
 
 
