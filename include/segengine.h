@@ -150,6 +150,28 @@ int seg_backward_range(seg_handle h, const float* dlogits, int zero_grads, int o
 int seg_backward_slice(seg_handle h, const float* dlogits, int zero_grads, int op_begin, int op_end, int join, void* stream);
 int seg_side_wait(seg_handle h, void* stream);
 
+/* ---- feature taps: the output of a named module as the passes left it in the workspace (what a forward / backward hook on that module would see).
+ * Taps of this version: "in_tr", "down_tr32", "down_tr64", "down_tr128", "down_tr256" - the input block and the four DownTransitions of the encoder that
+ * SEG_NET_VNET and SEG_NET_RESNET share (networks/VNet3d.py:25-59, ResNet3d.py:24-58); SEG_NET_UNET has none, and any other name is "not found".
+ * seg_feature_find: the tap's id (>= 0; valid for the life of the handle), its channels and its level (extents = input extents >> level); < 0 and
+ * seg_last_error() for an unknown name.
+ * seg_feature_read: out = the activation as fp32 NC[D]HW (n * channels * voxels floats of device memory); want_grad != 0: d(what the caller seeded the
+ * backward pass with) / d(that activation) instead - the contribution tensors of the tap summed in fp32 in the order the backward pass wrote them (a VNet
+ * skip level has two), divided by the handle's loss scale (dlogits are handed to seg_backward times that scale).
+ * Validity is tracked by the handle: the activation is readable after a seg_forward at the current plan, the gradient after a COMPLETE backward pass of
+ * that forward (seg_backward, or every slice of the op list in order).  seg_plan, seg_bind, seg_train_step and seg_train_graph_launch leave nothing to
+ * read, and a seg_set_loss_scale that changes the scale leaves no gradient (the tensors carry the old one); every such call fails with a message that names what is missing, as does a contribution that is never written (virtual).
+ * Nothing here changes the plan: no workspace byte, no op of the forward or backward lists. */
+int seg_feature_find(seg_handle h, const char* name, int* channels, int* level);
+int seg_feature_read(seg_handle h, int id, int want_grad, float* out, void* stream);
+/* Grad-CAM (model/visualization.py:112-238 of the reference) of nlayers (1..16) taps from the tensors of the last forward and backward pass (validity as
+ * for seg_feature_read with want_grad): per layer the map of seg_op_gradcam below with weight 1 / nlayers, accumulated in `out` in the order of `ids`,
+ * finalized after the last.  out: fp32 [N][D]HW at the input resolution, values in [0, 1].  For the reference's map the backward pass is seeded with
+ * dlogits = loss scale at [n][target class of sample n], 0 elsewhere.  ws: seg_gradcam_ws_bytes() bytes (any nlayers: the layers share it), 256-byte
+ * aligned; no allocation, no host synchronisation, two calls on the same tensors agree bit for bit. */
+long long seg_gradcam_ws_bytes(seg_handle h, int nlayers);
+int seg_gradcam(seg_handle h, const int* ids, int nlayers, void* ws, float* out, void* stream);
+
 int seg_set_loss_scale(seg_handle h, float scale);
 float seg_get_loss_scale(seg_handle h);
 
@@ -510,6 +532,22 @@ int seg_op_cls_head_forward(const void* act, const float* w1, const float* b1, c
                             long long v, int c, void* ws, int dtype, void* stream);
 int seg_op_cls_head_backward(const float* dlogits, const float* w1, const float* w2, float* dw1, float* db1, float* dw2, float* db2, void* dact, int n,
                              long long v, int c, int zero_grads, void* ws, int dtype, void* stream);
+/* Grad-CAM of one layer (csrc/gradcam.hip; model/visualization.py:135-193 of the reference) on act / grad [N][ID][IH][IW][C] in the run dtype, C in
+ * {16, 32, 64, 128, 256}, grad = (gradient of the class score) / inv_loss_scale.  Per sample n:
+ *   w[c] = inv_loss_scale * mean_v grad[n][v][c]          fp64 sums per 512-voxel slab, folded over ascending slabs, rounded once to fp32
+ *   cam[v] = max(0, sum_c w[c] act[n][v][c])               fp32 fmaf chain
+ *   s = (cam - min cam) / (1e-7 + (max cam - min cam))     min / max over the sample (a constant cam, one voxel included, gives s = 0)
+ *   r = s resized to (OD, OH, OW): linear along every axis, source coordinate (o + 0.5) * in / out - 0.5 clamped to the axis - cv2 INTER_LINEAR as
+ *       published (cv2.resize itself is not pinned: the reference needs it, this project's tests do not have it), which equals
+ *       F.interpolate(mode = "bilinear" / "trilinear", align_corners = False) when enlarging
+ *   out[n] = weight * r (accumulate = 0)  or  out[n] + weight * r (accumulate != 0)
+ *   finalize != 0: then out[n] = (q - min q) / (1e-7 + (max q - min q)), q = max(0, out[n])   (aggregate_multi_layers)
+ * so a map over L layers is L calls with weight = 1 / L, accumulate = 0 for the first, finalize = 1 for the last.  ndim 2: ID = OD = 1.  act / grad
+ * 32-byte aligned; ws: seg_op_gradcam_ws_bytes() bytes, 256-byte aligned.  n 1..65535, id * ih * iw * c and od * oh * ow below 2^31.  Stream-ordered, no
+ * allocation, no readback, no floating-point atomics: two calls agree bit for bit. */
+long long seg_op_gradcam_ws_bytes(int n, int c, int id, int ih, int iw, int od, int oh, int ow);
+int seg_op_gradcam(const void* act, const void* grad, int dtype, int n, int c, int id, int ih, int iw, int od, int oh, int ow, int ndim, float inv_loss_scale,
+                   float weight, int accumulate, int finalize, void* ws, float* out, void* stream);
 
 /* ---- soft-clDice building blocks (model/lossescldice.py:5-59; corrected restatement).
  * Planar fp32 tensors [planes][D][H][W]; nd = 3 pools 3x3x3 over (D,H,W), nd = 2 pools 3x3 over (H,W); stride 1, pad 1,

@@ -53,6 +53,10 @@ SIGNATURES = {
     "seg_backward_range": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "seg_backward_slice": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "seg_side_wait": (_i, [_vp, _vp]),
+    "seg_feature_find": (_i, [_vp, C.c_char_p, C.POINTER(_i), C.POINTER(_i)]),
+    "seg_feature_read": (_i, [_vp, _i, _i, _vp, _vp]),
+    "seg_gradcam_ws_bytes": (_ll, [_vp, _i]),
+    "seg_gradcam": (_i, [_vp, C.POINTER(_i), _i, _vp, _vp, _vp]),
     "seg_set_loss_scale": (_i, [_vp, _f]),
     "seg_get_loss_scale": (_f, [_vp]),
     "seg_loss_ws_bytes": (_ll, [_i, _i]),
@@ -100,6 +104,8 @@ SIGNATURES = {
     "seg_op_cls_head_ws_offset": (_ll, [_i, _ll, _i]),
     "seg_op_cls_head_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _vp, _i, _vp]),
     "seg_op_cls_head_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _i, _vp, _i, _vp]),
+    "seg_op_gradcam_ws_bytes": (_ll, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "seg_op_gradcam": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp]),
     "seg_op_pool3": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "seg_op_skel_iter": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "seg_op_skel_iter_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -579,6 +579,35 @@ int seg_op_cls_head_backward(const float* dlogits, const float* w1, const float*
     return SEG_OK("seg_op_cls_head_backward");
 }
 
+static const char* gradcam_shape_error(int n, int c, int id, int ih, int iw, int od, int oh, int ow) {
+    if (n < 1 || n > 65535) return "n must be 1..65535";
+    if (c != 16 && c != 32 && c != 64 && c != 128 && c != 256) return "c must be 16, 32, 64, 128 or 256";
+    if (id < 1 || ih < 1 || iw < 1 || od < 1 || oh < 1 || ow < 1) return "every extent must be >= 1";
+    if ((long long)id * ih * iw >= (1ll << 31) / c || (long long)od * oh * ow >= (1ll << 31)) return "id * ih * iw * c and od * oh * ow must stay below 2^31";
+    return nullptr;
+}
+long long seg_op_gradcam_ws_bytes(int n, int c, int id, int ih, int iw, int od, int oh, int ow) {
+    if (const char* err = gradcam_shape_error(n, c, id, ih, iw, od, oh, ow)) return fail(std::string("seg_op_gradcam_ws_bytes: ") + err);
+    return (long long)gradcam_ws_bytes(n, c, (long long)id * ih * iw, (long long)od * oh * ow);
+}
+int seg_op_gradcam(const void* act, const void* grad, int dtype, int n, int c, int id, int ih, int iw, int od, int oh, int ow, int ndim, float inv_loss_scale,
+                   float weight, int accumulate, int finalize, void* ws, float* out, void* stream) {
+    if (!act || !grad || !ws || !out) return fail("seg_op_gradcam: null pointer");
+    if (dtype < DT_F32 || dtype > DT_BF16) return fail("seg_op_gradcam: unknown dtype");
+    if (ndim != 2 && ndim != 3) return fail("seg_op_gradcam: ndim must be 2 or 3");
+    if (ndim == 2 && (id != 1 || od != 1)) return fail("seg_op_gradcam: ndim 2 takes id = od = 1");
+    if (const char* err = gradcam_shape_error(n, c, id, ih, iw, od, oh, ow)) return fail(std::string("seg_op_gradcam: ") + err);
+    if (!(inv_loss_scale > 0.f) || !std::isfinite(inv_loss_scale) || !(weight > 0.f) || !std::isfinite(weight))
+        return fail("seg_op_gradcam: inv_loss_scale and weight must be positive and finite");
+    if (((uintptr_t)act | (uintptr_t)grad) & 31) return fail("seg_op_gradcam: act and grad must be 32-byte aligned");
+    if ((uintptr_t)ws & 255) return fail("seg_op_gradcam: the workspace must be 256-byte aligned");
+    GradCamArgs a{};
+    a.act = act; a.grad[0] = grad; a.ngrad = 1; a.out = out; a.N = n; a.C = c; a.ID = id; a.IH = ih; a.IW = iw; a.OD = od; a.OH = oh; a.OW = ow;
+    a.inv_scale = inv_loss_scale; a.weight = weight; a.accumulate = accumulate ? 1 : 0; a.finalize = finalize ? 1 : 0; a.ws = (char*)ws;
+    launch_gradcam_layer(a, dtype, (hipStream_t)stream);
+    return SEG_OK("seg_op_gradcam");
+}
+
 int seg_op_pool3(const float* x, float* out, int planes, int d, int h, int w, int nd, int is_min, void* stream) {
     if (!x || !out || (nd != 2 && nd != 3)) return fail("seg_op_pool3: bad arguments");
     launch_pool3(x, out, planes, d, h, w, nd, is_min, (hipStream_t)stream);

@@ -104,6 +104,7 @@ int seg_plan(seg_handle h, int n, int d, int hgt, int wid) {
     if (h->side) { (void)hipStreamSynchronize(h->side); h->pack_bwd_pending = false; }
     h->drop_graph();
     h->N = n; h->D = d; h->H = hgt; h->W = wid;
+    h->taps_fwd = h->taps_bwd = false;
     g_err.clear();
     plan_engine(*h);
     if (!g_err.empty()) return -1;
@@ -130,6 +131,7 @@ int seg_bind(seg_handle h, float* params, float* grads, void* workspace) {
     if (h->side) { (void)hipStreamSynchronize(h->side); h->pack_bwd_pending = false; }     // see seg_plan
     h->drop_graph();
     h->p = params; h->g = grads; h->ws = (char*)workspace;
+    h->taps_fwd = h->taps_bwd = false;
     // resolve and upload the weight re-layout descriptors; reset the device-side step counter
     std::vector<PackDesc> d = h->packdescs;
     for (auto& x : d) {
@@ -185,8 +187,12 @@ int seg_forward(seg_handle h, const float* x, int mask_mode, const float* masks,
         ++h->draws;
     }
     h->cur_x = x; h->cur_logits = logits; h->cur_probs = probs;
+    h->taps_fwd = h->taps_bwd = false;
+    h->bwd_next = 0;
     h->run_ops(h->fwd_ops, 0, (int)h->fwd_ops.size(), st);
-    return hipGetLastError() == hipSuccess ? 0 : fail(std::string("seg_forward: ") + hipGetErrorString(hipGetLastError()));
+    if (hipGetLastError() != hipSuccess) return fail(std::string("seg_forward: ") + hipGetErrorString(hipGetLastError()));
+    h->taps_fwd = true;
+    return 0;
 }
 
 static int backward_slice(seg_handle h, const float* dlogits, int zero_grads, int op_begin, int op_end, int join, void* stream);
@@ -214,10 +220,15 @@ static int backward_slice(seg_handle h, const float* dlogits, int zero_grads, in
     h->cur_dlogits = dlogits;
     if (op_begin == 0) { h->ready_used = 0; h->hold_open = false; h->n_event_forks = 0; }
     if (h->pack_bwd_pending) { (void)hipStreamWaitEvent(st, h->pack_done, 0); h->pack_bwd_pending = false; }
+    // the gradient tensors are those of the last forward pass once every op has run, in order, since that pass (seg_feature_read, seg_gradcam)
+    h->taps_bwd = false;
+    h->bwd_next = (op_begin == 0 || op_begin == h->bwd_next) ? op_end : -1;
     h->run_ops(h->bwd_ops, op_begin, op_end, st);
     if (join) h->join_side(st);
     else h->flush_side(st);                              // the queued weight gradients of this slice are released; `stream` does not wait for them
-    return hipGetLastError() == hipSuccess ? 0 : fail(std::string("seg_backward: ") + hipGetErrorString(hipGetLastError()));
+    if (hipGetLastError() != hipSuccess) return fail(std::string("seg_backward: ") + hipGetErrorString(hipGetLastError()));
+    h->taps_bwd = h->taps_fwd && h->bwd_next == nops;
+    return 0;
 }
 int seg_backward(seg_handle h, const float* dlogits, int zero_grads, void* stream) {
     if (check_handle(h)) return -1;
@@ -243,10 +254,94 @@ int seg_backward_bucket(seg_handle h, double tail_fraction, int* op_split, long 
     return 0;
 }
 
+// ---- feature taps and Grad-CAM: read-only views of what a forward / backward pass left in the workspace; no op of the plan changes
+static const seg_engine::Tap* tap_of(seg_handle h, int id) {
+    for (auto& t : h->taps) if (t.ten == id) return &t;
+    return nullptr;
+}
+// the tap's tensors are there to be read: 0, or the error naming what is missing.  grads: the contribution tensors of the gradient are wanted too
+static int tap_ready(seg_handle h, const char* who, int id, bool grads) {
+    const seg_engine::Tap* t = tap_of(h, id);
+    if (!t) return fail(std::string(who) + ": not the id of a feature tap (seg_feature_find)");
+    if (!h->ws || !h->taps_fwd)
+        return fail(std::string(who) + ": '" + t->name + "' holds no activation: no seg_forward at the current plan precedes this call (a re-plan, a re-bind "
+                    "and seg_train_step leave nothing to read)");
+    if (!grads) return 0;
+    if (!h->taps_bwd)
+        return fail(std::string(who) + ": '" + t->name + "' holds no gradient: it needs a complete backward pass (seg_backward, or every slice in order) of "
+                    "the last seg_forward");
+    const std::vector<int>& gl = h->tens[id].grads;
+    if (gl.empty() || gl.size() > 3) return fail(std::string(who) + ": internal: '" + t->name + "' has no gradient tensor");
+    for (int gi : gl)
+        if (h->tens[gi].virt) return fail(std::string(who) + ": a gradient contribution of '" + t->name + "' is virtual (never written)");
+    return 0;
+}
+int seg_feature_find(seg_handle h, const char* name, int* channels, int* level) {
+    if (check_handle(h)) return -1;
+    if (!name) return fail("seg_feature_find: name is null");
+    for (auto& t : h->taps)
+        if (t.name == name) {
+            if (channels) *channels = h->tens[t.ten].C;
+            if (level) *level = h->tens[t.ten].lvl;
+            return t.ten;
+        }
+    std::string known;
+    for (auto& t : h->taps) known += (known.empty() ? "" : ", ") + t.name;
+    return fail(std::string("seg_feature_find: no feature tap '") + name + "' in this network (taps: " + (known.empty() ? "none" : known) + ")");
+}
+int seg_feature_read(seg_handle h, int id, int want_grad, float* out, void* stream) {
+    if (check_handle(h)) return -1;
+    if (!out) return fail("seg_feature_read: out is null");
+    if (tap_ready(h, "seg_feature_read", id, want_grad != 0)) return -1;
+    const Ten& t = h->tens[id];
+    const void* src[3] = {h->ws + t.off, nullptr, nullptr};
+    int nsrc = 1;
+    if (want_grad) {
+        nsrc = (int)t.grads.size();
+        for (int i = 0; i < nsrc; ++i) src[i] = h->ws + h->tens[t.grads[i]].off;
+    }
+    launch_feature_unpack(src, nsrc, out, h->N, t.C, h->vol(t.lvl), want_grad ? 1.f / h->loss_scale : 1.f, h->dtype, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : fail("seg_feature_read: launch failed");
+}
+long long seg_gradcam_ws_bytes(seg_handle h, int nlayers) {
+    if (check_handle(h)) return -1;
+    if (!h->planned) return fail("seg_gradcam_ws_bytes: call seg_plan first");
+    if (nlayers < 1 || nlayers > 16) return fail("seg_gradcam_ws_bytes: nlayers must be 1..16");
+    if (h->taps.empty()) return fail("seg_gradcam_ws_bytes: this network has no feature taps");
+    size_t b = 0;                       // the layers run one after another through the same scratch
+    for (auto& t : h->taps) b = std::max(b, gradcam_ws_bytes(h->N, h->tens[t.ten].C, h->vol(h->tens[t.ten].lvl), h->vol(0)));
+    return (long long)b;
+}
+int seg_gradcam(seg_handle h, const int* ids, int nlayers, void* ws, float* out, void* stream) {
+    if (check_handle(h)) return -1;
+    if (!ids || !ws || !out) return fail("seg_gradcam: null pointer");
+    if (nlayers < 1 || nlayers > 16) return fail("seg_gradcam: nlayers must be 1..16");
+    if ((uintptr_t)ws & 255) return fail("seg_gradcam: the workspace must be 256-byte aligned");
+    for (int i = 0; i < nlayers; ++i)
+        if (tap_ready(h, "seg_gradcam", ids[i], true)) return -1;
+    for (int i = 0; i < nlayers; ++i) {
+        const Ten& t = h->tens[ids[i]];
+        GradCamArgs a{};
+        a.act = h->ws + t.off;
+        a.ngrad = (int)t.grads.size();
+        for (int k = 0; k < a.ngrad; ++k) a.grad[k] = h->ws + h->tens[t.grads[k]].off;
+        a.out = out; a.N = h->N; a.C = t.C;
+        a.ID = h->dim_d(t.lvl); a.IH = h->dim_h(t.lvl); a.IW = h->dim_w(t.lvl);
+        a.OD = h->dim_d(0); a.OH = h->dim_h(0); a.OW = h->dim_w(0);
+        a.inv_scale = 1.f / h->loss_scale; a.weight = 1.f / (float)nlayers;
+        a.accumulate = i > 0; a.finalize = i == nlayers - 1; a.ws = (char*)ws;
+        launch_gradcam_layer(a, h->dtype, (hipStream_t)stream);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : fail("seg_gradcam: launch failed");
+}
+
 int seg_set_loss_scale(seg_handle h, float scale) {
     if (check_handle(h)) return -1;
     if (!(scale > 0.f)) return fail("seg_set_loss_scale: scale must be positive");
-    if (scale != h->loss_scale) h->drop_graph();          // the scale is baked into the captured launches
+    if (scale != h->loss_scale) {
+        h->drop_graph();          // the scale is baked into the captured launches
+        h->taps_bwd = false;      // ... and into the gradient tensors a backward pass left: seg_feature_read / seg_gradcam would divide them by the new one
+    }
     h->loss_scale = scale;
     return 0;
 }
@@ -268,7 +363,8 @@ int seg_train_step(seg_handle h, const seg_train_args* a, void* stream) {
     // ingest - nothing overlaps them): the one-wave bookkeeping launches ride on their neighbours.  SEG_STEP_RIDERS=0: separate launches.
     const bool riders = knob_i("SEG_STEP_RIDERS", 1) != 0;
     const long long v = h->out_vol();
-    struct RideGuard { seg_engine* e; ~RideGuard() { e->ride_on = false; e->ride_zero = nullptr; } } ride_guard{h};      // every way out of the step
+    // every way out of the step (the optimiser has moved the parameters on: the workspace no longer belongs to a forward pass a caller could name)
+    struct RideGuard { seg_engine* e; ~RideGuard() { e->ride_on = false; e->ride_zero = nullptr; e->taps_fwd = e->taps_bwd = false; } } ride_guard{h};
     h->ride_on = riders; h->head_zeroed = false;
     h->ride_ingest = StepRider{}; h->ride_pack = StepRider{};
     if (riders) {
@@ -410,6 +506,7 @@ int seg_train_graph_launch(seg_handle h, void* stream) {
     if (h->tgraph_mask_mode == SEG_MASKS_RANDOM) ++h->draws;
     h->tgraph_stream = (hipStream_t)stream;
     h->q_clean = false;          // the replayed backward pass used the GroupNorm-backward sums: an eager backward that follows must clear them
+    h->taps_fwd = h->taps_bwd = false;
     return 0;
 }
 int seg_train_graph_ready(seg_handle h) { return (h && h->tgraph_exec) ? 1 : 0; }

@@ -88,6 +88,13 @@ struct seg_engine {
     std::vector<Step> steps;
     std::vector<int> drop_ch;    // channels per dropout call
     int image_ten = -1;
+    // feature taps (seg_feature_find): the output tensor of in_tr and of the four DownTransitions (Builder::encoder)
+    struct Tap { std::string name; int ten; };
+    std::vector<Tap> taps;
+    // what the workspace holds of the current plan: the activations of a seg_forward, and the gradient tensors of a COMPLETE backward pass of that forward
+    // (bwd_next: the op the pass has reached).  seg_plan / seg_bind / seg_train_step / a graph replay clear both.
+    bool taps_fwd = false, taps_bwd = false;
+    int bwd_next = 0;
     bool pad_img = false;        // the image tensor is zero-padded to 16 channels: 3-D inputs with > 1 channel (2-D: > 3) cannot take the fused image stem
                                  // (one MFMA K step holds taps x channels <= 32) and run through the ordinary 16-channel convs instead
     // plan

@@ -118,6 +118,7 @@ struct Builder {
         const int ub = add_unit(ck1, w1, b1, x, -1, F, 0, gw, gb, all_drop);
         int prev = act(ua, ub, -1);
         skips.assign(1, prev);
+        e.taps.push_back({"in_tr", prev});
         const int nconv_down[4] = {2, 3, 3, 3};
         for (int l = 1; l <= 4; ++l) {   // DownTransition (VNet3d.py:46-59)
             const int C = F << l;
@@ -132,6 +133,7 @@ struct Builder {
             }
             prev = t;
             skips.push_back(prev);
+            e.taps.push_back({pre, prev});
         }
         return prev;
     }

@@ -114,6 +114,26 @@ size_t cls_head_ws_offset(int N, long long V, int what);      // 0 pooled [N][25
 void launch_cls_head_fwd(const ClsHeadArgs& a, int dtype, hipStream_t s);
 void launch_cls_head_bwd(const ClsHeadArgs& a, int dtype, hipStream_t s);
 
+// Grad-CAM (gradcam.hip; model/visualization.py:135-193 of the reference) of ONE layer: channel weights w[n][c] = mean_v sum_i grad[i][n][v][c] * inv_scale,
+// cam[n][v] = max(0, sum_c w[n][c] act[n][v][c]), min-max scaling per sample, linear resize (half-pixel centres, clamped edges) from (ID, IH, IW) to
+// (OD, OH, OW), out (+)= weight * resized; `finalize`: then out = minmax(max(0, out)) per sample.  Deterministic: no atomics, fixed fold orders.
+constexpr int GC_SLAB = 512, GC_OSLAB = 1024;      // voxels per workgroup of the layer passes / output voxels per workgroup of the resize and final passes
+struct GradCamArgs {
+    const void* act;         // [N][V][C] T, V = ID * IH * IW
+    const void* grad[3];     // 1 .. 3 gradient contributions [N][V][C] T (summed in this order), times 1 / inv_scale
+    int ngrad;
+    float* out;              // [N][OD][OH][OW] fp32: the accumulator over the layers, then the map
+    int N, C;                // C in {16, 32, 64, 128, 256}
+    int ID, IH, IW, OD, OH, OW;
+    float inv_scale, weight;
+    int accumulate, finalize;
+    char* ws;                // gradcam_ws_bytes
+};
+size_t gradcam_ws_bytes(int N, int C, long long V, long long OV);
+void launch_gradcam_layer(const GradCamArgs& a, int dtype, hipStream_t s);
+// out fp32 [N][C][V] = scale * sum_i src[i][n][v][c] (channels-last T -> planar; the export of a feature tap, seg_feature_read); C % 16 == 0
+void launch_feature_unpack(const void* const* src, int nsrc, float* out, int N, int C, long long V, float scale, int dtype, hipStream_t s);
+
 // GroupNorm(8) finalize: stats -> per-(n,c) scale/shift (dropout multiplier folded in) + mean/rstd
 struct GnFinArgs {
     const double* stats;  // [N][C][2]

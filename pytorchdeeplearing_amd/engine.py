@@ -8,6 +8,7 @@ HIP library through the C-ABI (include/segengine.h)."""
 import ctypes as C
 from collections import OrderedDict
 
+import numpy as np
 import torch
 
 from . import _capi
@@ -235,6 +236,67 @@ class SegEngine:
         k, off = C.c_int(0), C.c_longlong(0)
         self.lib.check(self.lib.seg_backward_bucket(self.h, float(tail_fraction), C.byref(k), C.byref(off)), "seg_backward_bucket")
         return k.value, off.value, self.lib.seg_backward_ops(self.h)
+
+    # ---- feature taps and Grad-CAM ---------------------------------------------------------------
+    FEATURE_NAMES = ("in_tr", "down_tr32", "down_tr64", "down_tr128", "down_tr256")
+
+    def _feature_id(self, name):
+        ch, lvl = C.c_int(), C.c_int()
+        fid = self.lib.seg_feature_find(self.h, str(name).encode(), C.byref(ch), C.byref(lvl))
+        self.lib.check(fid, "seg_feature_find")
+        return fid, ch.value, lvl.value
+
+    def feature(self, name, grad=False):
+        """The output of the module `name` (one of FEATURE_NAMES: the encoder blocks of the VNets and the classifiers) as the last forward pass left it:
+        fp32 NC[D]HW.  grad=True: the gradient of what the last complete backward pass was seeded with wrt that output, loss scale divided out.  The
+        library tracks validity: a read without the pass it needs (or after train_step / a re-plan) raises with the library's message."""
+        fid, ch, lvl = self._feature_id(name)
+        if self.shape is None:
+            raise RuntimeError("segengine feature: no forward pass yet")
+        out = torch.empty((self.shape[0], ch) + tuple(s >> lvl for s in self.shape[1:]), dtype=torch.float32, device=self.device)
+        self.lib.check(self.lib.seg_feature_read(self.h, fid, 1 if grad else 0, _ptr(out), self.stream()), "seg_feature_read")
+        return out
+
+    def grad_cam(self, x, target_category, names):
+        """Grad-CAM (model/visualization.py:112-238 of the reference) of the modules `names` (FEATURE_NAMES) for the batch x: fp32 (N, [D,] H, W) on the
+        device, values in [0, 1].  target_category: one class index (an int, a 0-d array or tensor), one per sample, or None for each sample's arg-max
+        class of this call's own forward pass (numclass == 1: the only column, 0); the classes used are left in self.last_cam_categories.
+        Runs an eval-mode forward pass, a FULL backward pass seeded with the one-hot of the target classes, and the map kernels (seg_gradcam).  The
+        backward pass zeroes and overwrites self.grads (the parameter gradients) - the reference calls model.zero_grad() too."""
+        names = list(names)
+        if not names:
+            raise ValueError("grad_cam: no target layer given")
+        if not self.classifier:
+            raise ValueError("grad_cam: the class score of a sample is defined for the classifiers (kind 'resnet') only")
+        n = x.shape[0]
+        cats = None
+        if target_category is not None:
+            if torch.is_tensor(target_category):
+                target_category = target_category.detach().cpu().tolist()
+            cats = [int(target_category)] * n if np.ndim(target_category) == 0 else [int(c) for c in target_category]
+            if len(cats) != n or any(c < 0 or c >= self.numclass for c in cats):
+                raise ValueError("grad_cam: target_category must be one class index in [0, %d) or one per sample" % self.numclass)
+        for nm in names:
+            self._feature_id(nm)
+        _, probs = self.forward(x, _capi.MASKS_EVAL)
+        if cats is None:
+            cats = torch.argmax(probs, dim=1).cpu().tolist()
+        self.last_cam_categories = cats
+        dl = torch.zeros((n, self.numclass), dtype=torch.float32)
+        dl[torch.arange(n), torch.tensor(cats)] = self.loss_scale
+        self.backward(dl.to(self.device), zero_grads=True)
+        return self.last_pass_cam(names)
+
+    def last_pass_cam(self, names):
+        """the Grad-CAM map of the modules `names` from the tensors the last forward and (complete) backward pass left (seg_gradcam): what grad_cam ends
+        with, for a caller that seeds the backward pass itself or wants several layer sets of one pass"""
+        ids = (C.c_int * len(names))(*[self._feature_id(nm)[0] for nm in names])
+        nbytes = self.lib.seg_gradcam_ws_bytes(self.h, len(names))
+        self.lib.check(nbytes, "seg_gradcam_ws_bytes")
+        ws = aligned_empty(nbytes, self.device)
+        out = torch.empty(self.shape, dtype=torch.float32, device=self.device)
+        self.lib.check(self.lib.seg_gradcam(self.h, ids, len(names), _ptr(ws), _ptr(out), self.stream()), "seg_gradcam")
+        return out
 
     # ---- losses ---------------------------------------------------------------------------------
     def loss_forward(self, logits, target, loss_name, focal_alpha=0.25, focal_gamma=2.0, class_alpha=None, out3=None, exchange=None):

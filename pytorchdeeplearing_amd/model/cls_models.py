@@ -7,7 +7,9 @@ Where the reference cannot run as shipped:
   * networks/ResNet3d.py:51 reads an undefined global `prob`; the engine uses p = 0.2, the VNet value;
   * in train mode the reference's `loss.backward()` raises (the in-place dropout overwrites what the in-place ReLU saved); the step here is the
     backward pass of the same function;
-  * `_loss_function` compares strings with `is`; `==` is used.
+  * `_loss_function` compares strings with `is`; `==` is used;
+  * `Grad_CAM_Visual` hands `self.model` to visualization.GradCAM, which unpacks (logits, softmax, argmax) from `model(x)` - ResNet2d.forward returns the
+    logits alone, so the call raises; the map here is the one the class computes when handed that triple (tests/golden/gradcam_2d.npz).
 Reproduced as written: `calc_accuracy` on the binary wrappers' (N, 1) against (N,) tensors (see metric.calc_accuracy); `optim.Adam` (coupled weight
 decay 0); the checkpoint is written whenever the epoch-mean validation accuracy improves."""
 import os
@@ -22,7 +24,7 @@ from torch.utils.data import DataLoader
 from .. import _capi, metric as M, networks
 from . import _io
 from .dataset import datasetModelClassifywithnpy, datasetModelClassifywithopencv
-from .visualization import plot_result
+from .visualization import GradCAM, plot_result
 
 _LOSSES = {True: ("BinaryCrossEntropyLoss", "BinaryFocalLoss"), False: ("MutilCrossEntropyLoss", "MutilFocalLoss")}
 
@@ -163,6 +165,31 @@ class _ClsModel(object):
         d, h, w = np.shape(image)[0], np.shape(image)[1], np.shape(image)[2]      # modelResNet.py:638-647
         return self.predict(np.transpose(np.reshape(image, (d, h, w, 1)), (3, 0, 1, 2)))
 
+    def Grad_CAM_Visual(self, full_img, target_category, target_layers):
+        """Grad-CAM of one image (C, H, W) / volume (C, D, H, W) (modelResNet.py:419-426): float32 of the input's spatial shape, values in [0, 1].
+        target_layers: module objects out of self.model.in_tr, .down_tr32, .down_tr64, .down_tr128, .down_tr256 (visualization.GradCAM); target_category: the
+        class index, or None for the arg-max class.  The reference has this method on MutilResNet2dModel only; the other three wrappers and the 3-D maps
+        (trilinear resize) are extensions.  The call overwrites the parameter gradients (the reference's GradCAM calls model.zero_grad() too).
+
+        16-bit run dtypes: the channel weights and the weighted sum are cancelling sums at the shallow layers (the raw map of in_tr spans +-2e-3), so 16-bit
+        storage of activations and gradients moves single pixels by tenths there - in stock PyTorch under torch.autocast as in the engine.  Measured
+        on MI355X against the float64 map (tests/test_gradcam_lowp.py: three test networks, every class; engine / torch.autocast on the same device):
+            layer         f16 worst |d|    f16 mean |d|       bf16 worst |d|   bf16 mean |d|
+            down_tr256    2.6e-3           -                  6.4e-2           -
+            down_tr128    0.10 / 0.13      0.0048 / 0.0051    0.43 / 0.14      0.017 / 0.018
+            down_tr64     0.14 / 0.16      0.0089 / 0.0093    0.25 / 0.31      0.027 / 0.027
+            down_tr32     0.20 / 0.26      0.014  / 0.014     0.47 / 0.52      0.032 / 0.035
+            in_tr         0.36 / 0.31      0.011  / 0.012     0.50 / 0.93      0.023 / 0.027
+        For attribution at the shallow layers construct the network with dtype="f32" (SEGENGINE_DTYPE=f32): maps within 4e-6 of float64."""
+        if not len(target_layers):
+            raise NotImplementedError("Grad_CAM_Visual needs the activation of a target layer and its gradient, and no target layer was given "
+                                      "(pass modules of self.model: in_tr, down_tr32, down_tr64, down_tr128, down_tr256)")
+        input_tensor = torch.as_tensor(np.asarray(full_img)).float().contiguous().unsqueeze(0).to(device=self.device, dtype=torch.float32)
+        with self._lock:
+            cam = GradCAM(model=self.model, target_layers=target_layers, use_cuda=self.use_cuda)
+            grayscale_cam = cam(input_tensor=input_tensor, target_category=target_category)
+        return grayscale_cam[0]
+
     def clear_GPU_cache(self):
         if self.device.type == "cuda":
             torch.cuda.empty_cache()
@@ -184,10 +211,6 @@ class MutilResNet2dModel(_ClsModel):
     def __init__(self, image_height, image_width, image_channel, numclass, batch_size, loss_name="MutilFocalLoss", inference=False, model_path=None,
                  use_cuda=True):
         self._init((image_height, image_width), image_channel, numclass, batch_size, loss_name, inference, model_path, use_cuda)
-
-    def Grad_CAM_Visual(self, full_img, target_category, target_layers):
-        raise NotImplementedError("Grad_CAM_Visual needs the activation of a target layer and its gradient; the engine keeps its activations channels-last "
-                                  "in a private workspace and exposes neither (no forward / backward hooks on the sub-modules, which only hold parameters)")
 
 
 class BinaryResNet3dModel(_ClsModel):

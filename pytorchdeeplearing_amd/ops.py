@@ -528,3 +528,24 @@ def cls_head_backward(fwd, dlogits, w1, w2, dtype, grads=None, zero_grads=True):
                                            g["db2"].data_ptr(), dact.data_ptr(), N, V, C_, 1 if zero_grads else 0, ws.data_ptr(), _capi.DTYPE[dtype],
                                            _capi.stream_for(ws.device)), "seg_op_cls_head_backward")
     return dict(g, dact=dact)
+
+
+def gradcam_layer(act, grad, dtype, out_size, out=None, inv_loss_scale=1.0, weight=1.0, accumulate=False, finalize=True, ws=None):
+    """Grad-CAM of one layer (seg_op_gradcam) on act / grad [N, D, H, W, C] or [N, H, W, C] in the run dtype: the map fp32 [N, *out_size].  A map over L
+    layers: L calls on the same `out` with weight = 1 / L, accumulate = False for the first and finalize = True for the last."""
+    lib = _capi.lib_for(act.device)
+    nd = act.dim() - 2
+    assert nd in (2, 3) and len(out_size) == nd and act.shape == grad.shape
+    assert act.dtype == grad.dtype == TORCH_DTYPE[dtype] and act.is_contiguous() and grad.is_contiguous()
+    N, C_ = act.shape[0], act.shape[-1]
+    ie = ((1,) if nd == 2 else ()) + tuple(int(s) for s in act.shape[1:-1])
+    oe = ((1,) if nd == 2 else ()) + tuple(int(s) for s in out_size)
+    nbytes = lib.seg_op_gradcam_ws_bytes(N, C_, *ie, *oe)
+    lib.check(nbytes, "seg_op_gradcam_ws_bytes")
+    if ws is None:
+        ws = aligned_empty(nbytes, act.device)
+    if out is None:
+        out = _alloc((N,) + tuple(int(s) for s in out_size), torch.float32, act.device)
+    lib.check(lib.seg_op_gradcam(act.data_ptr(), grad.data_ptr(), _capi.DTYPE[dtype], N, C_, *ie, *oe, nd, float(inv_loss_scale), float(weight),
+                                 1 if accumulate else 0, 1 if finalize else 0, ws.data_ptr(), out.data_ptr(), _capi.stream_for(act.device)), "seg_op_gradcam")
+    return out
