@@ -21,6 +21,9 @@
  *                        kernel whose workgroups exchange their partial sums inside the launch
  *   SEG_HEAD_FUSE=0      (read per seg_create) the 1^d head (networks/VNet3d.py:83-99) as a launch of its own instead of inside the activation pass that produces its
  *                        input (bit-identical results)
+ *   SEG_HEAD_WFUSE=0|2   (read per seg_create) weight / bias gradient of a ONE-class head: 0 = head_bwd_kernel reads the head's input; otherwise the
+ *                        GroupNorm-backward reduce passes of the units that input is made of collect it (they hold dlogits and the activations already) and
+ *                        seg_train_step does not write the head's input at all - default on tensors >= 16 MB, 2 = at every size.  Other heads: no effect
  *   SEG_RQ_FUSE=0        (read per seg_create) the GroupNorm-backward reduction of a VNet up-conv unit as a launch of its own instead of riding on the
  *                        data-gradient launch of the 1^d conv that produces its gradient
  *   SEG_VACT=0|2         (read per seg_create) the activation between a VNet up-conv and the 1^d conv on the concat (networks/VNet3d.py:72-77): 0 = written as a
@@ -115,7 +118,8 @@ int seg_set_dropout_draws(seg_handle h, long long draws);
 int seg_plan(seg_handle h, int n, int d, int hgt, int wid);
 long long seg_workspace_bytes(seg_handle h);
 /* what the planner decided for the current shape (tests / diagnostics): what = 1: convolution units, 2: fork events the last backward pass recorded
- * on the caller's stream.  <0: not planned / unknown `what`. */
+ * on the caller's stream, 3: 1 where the head's weight gradient comes out of the GroupNorm-backward reduce passes (SEG_HEAD_WFUSE), else 0.
+ * <0: not planned / unknown `what`. */
 int seg_plan_count(seg_handle h, int what);
 
 /* Bind caller-owned buffers: flat fp32 params / grads (seg_param_numel floats each) + workspace. */
@@ -152,7 +156,8 @@ int seg_side_wait(seg_handle h, void* stream);
 
 /* ---- feature taps: the output of a named module as the passes left it in the workspace (what a forward / backward hook on that module would see).
  * Taps of this version: "in_tr", "down_tr32", "down_tr64", "down_tr128", "down_tr256" - the input block and the four DownTransitions of the encoder that
- * SEG_NET_VNET and SEG_NET_RESNET share (networks/VNet3d.py:25-59, ResNet3d.py:24-58); SEG_NET_UNET has none, and any other name is "not found".
+ * SEG_NET_VNET and SEG_NET_RESNET share (networks/VNet3d.py:25-59, ResNet3d.py:24-58) - and, SEG_NET_VNET only, "up_tr32": the last UpTransition, the head's
+ * input (its gradient is virtual under a one-class head); SEG_NET_UNET has none, and any other name is "not found".
  * seg_feature_find: the tap's id (>= 0; valid for the life of the handle), its channels and its level (extents = input extents >> level); < 0 and
  * seg_last_error() for an unknown name.
  * seg_feature_read: out = the activation as fp32 NC[D]HW (n * channels * voxels floats of device memory); want_grad != 0: d(what the caller seeded the
@@ -511,6 +516,11 @@ typedef struct seg_gn_bwd_args {
     int rep_q, rep_s; int path;
 } seg_gn_bwd_args;
 int seg_op_gn_backward(const seg_gn_bwd_args* a, int dtype, void* stream);
+/* The same (SEPARATE / FOLD paths, one branch, the virtual source of a one-class head: vK == 1, ndy 0 or 1, C <= 128), and the reduce launch also collects
+ * the head's weight gradient: head_dw[c] += sum_{n,v} vdl[n][v] * act[n][v][c], act = relu(scale * r + shift) - in fp32 for ndy == 0, which also gives
+ * head_db[0] += sum vdl; rounded to the run dtype (the activation as a forward pass stores it) for ndy == 1, head_db untouched.  head_sums: scratch
+ * shaped like Q, ZERO at the call. */
+int seg_op_gn_backward_head(const seg_gn_bwd_args* a, double* head_sums, float* head_dw, float* head_db, int dtype, void* stream);
 /* the co-operative kernel's plan for a shape (esz: bytes per element): 1 and *S workgroups per (sample, group), *ku chunks per thread; 0: not eligible */
 int seg_op_gn_coop_plan(int c, long long v, int n, int esz, int* S, int* ku);
 int seg_op_gn_group_eligible(int c, long long v, int esz);

@@ -97,6 +97,7 @@ SIGNATURES = {
     "seg_abi_sizeof": (_i, [_i]),
     "seg_op_gn_forward": (_i, [_vp, _i, _vp]),
     "seg_op_gn_backward": (_i, [_vp, _i, _vp]),
+    "seg_op_gn_backward_head": (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
     "seg_op_gn_coop_plan": (_i, [_i, _ll, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "seg_op_gn_group_eligible": (_i, [_i, _ll, _i]),
     "seg_op_maxpool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

@@ -479,7 +479,14 @@ int seg_op_gn_forward(const seg_gn_fwd_args* a, int dtype, void* stream) {
     return SEG_OK("seg_op_gn_forward");
 }
 
-int seg_op_gn_backward(const seg_gn_bwd_args* a, int dtype, void* stream) {
+static int gn_backward_impl(const seg_gn_bwd_args* a, const GnHeadW* hw, int dtype, void* stream);
+int seg_op_gn_backward(const seg_gn_bwd_args* a, int dtype, void* stream) { return gn_backward_impl(a, nullptr, dtype, stream); }
+int seg_op_gn_backward_head(const seg_gn_bwd_args* a, double* head_sums, float* head_dw, float* head_db, int dtype, void* stream) {
+    if (!head_sums || !head_dw || !head_db) return fail("seg_op_gn_backward_head: null pointer");
+    const GnHeadW hw{head_sums, head_dw, head_db};
+    return gn_backward_impl(a, &hw, dtype, stream);
+}
+static int gn_backward_impl(const seg_gn_bwd_args* a, const GnHeadW* hw, int dtype, void* stream) {
     if (!a || !a->r || !a->scale || !a->shift || !a->mean || !a->rstd || !a->stats || !a->gamma || !a->Q || !a->dr || !a->dgamma || !a->dbeta)
         return fail("seg_op_gn_backward: null pointer");
     if (a->r2 && (!a->scale2 || !a->shift2 || !a->mean2 || !a->rstd2 || !a->stats2 || !a->gamma2 || !a->Q2 || !a->dr2 || !a->dgamma2 || !a->dbeta2))
@@ -508,6 +515,8 @@ int seg_op_gn_backward(const seg_gn_bwd_args* a, int dtype, void* stream) {
     f2.Q = a->Q2; f2.stats = a->stats2; f2.gamma = a->gamma2; f2.mask = a->mask2; f2.mean = a->mean2; f2.rstd = a->rstd2;
     f2.dgamma = a->dgamma2; f2.dbeta = a->dbeta2; f2.dbias = a->dbias2; f2.coef = a->coef2;
     hipStream_t st = (hipStream_t)stream;
+    if (hw && ((a->path != SEG_GN_BWD_SEPARATE && a->path != SEG_GN_BWD_FOLD) || !gn_head_w_supported(e)))
+        return fail("seg_op_gn_backward_head: reduce + apply paths only, with the virtual source of a one-class head (vK == 1), one branch, 0 or 1 stored sources, C <= 128");
     if (a->path == SEG_GN_BWD_COOP) {
         if (!gn_bwd_coop_eligible(e, esz)) return fail("seg_op_gn_backward: not eligible for the co-operative kernel (1..3 stored sources, one branch, seg_op_gn_coop_plan)");
         launch_gn_bwd_coop(e, f, dtype, st);
@@ -517,12 +526,12 @@ int seg_op_gn_backward(const seg_gn_bwd_args* a, int dtype, void* stream) {
         launch_gn_bwd_group(e, f, dtype, st);
     } else {
         if (a->path == SEG_GN_BWD_SEPARATE && (!a->coef || (a->r2 && !a->coef2))) return fail("seg_op_gn_backward: null pointer (coef)");
-        launch_gn_bwd_reduce(e, dtype, st);
+        launch_gn_bwd_reduce(e, dtype, st, hw);
         if (a->path == SEG_GN_BWD_SEPARATE) {
             if (a->r2) launch_gn_bwd_finalize(f, st, &f2);
             else launch_gn_bwd_finalize(f, st);
-            launch_gn_bwd_apply(e, dtype, st);
-        } else launch_gn_bwd_apply(e, dtype, st, &f, a->r2 ? &f2 : nullptr);
+            launch_gn_bwd_apply(e, dtype, st, nullptr, nullptr, hw);
+        } else launch_gn_bwd_apply(e, dtype, st, &f, a->r2 ? &f2 : nullptr, hw);
     }
     return SEG_OK("seg_op_gn_backward");
 }

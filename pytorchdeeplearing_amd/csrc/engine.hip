@@ -38,6 +38,7 @@ int seg_create(int net_kind, int ndim, int in_channels, int num_class, int init_
     e->use_coop = knob_i("SEG_GN_COOP", e->use_coop) != 0;
     e->use_vact = knob_i("SEG_VACT", e->use_vact);
     e->use_head_fuse = knob_i("SEG_HEAD_FUSE", e->use_head_fuse) != 0;
+    e->use_head_wfuse = knob_i("SEG_HEAD_WFUSE", e->use_head_wfuse);
     e->use_rq_fuse = knob_i("SEG_RQ_FUSE", e->use_rq_fuse) != 0;
 #ifdef SEG_DIAG
     e->w3_mode = knob_i("SEG_DIAG_W3_MODE", e->w3_mode);
@@ -114,6 +115,7 @@ int seg_plan(seg_handle h, int n, int d, int hgt, int wid) {
 int seg_plan_count(seg_handle h, int what) {
     if (!h || !h->planned) return -1;
     if (what == 2) return h->n_event_forks;             // last backward pass: fork events recorded on the main stream
+    if (what == 3) return h->head_w_act >= 0 ? 1 : 0;   // the head's weight gradient comes out of the GroupNorm-backward reduce passes (SEG_HEAD_WFUSE)
     int n = 0;
     for (auto& s : h->steps) {
         if (what == 1) n += s.type == ST_UNIT;                                            // convolution units
@@ -364,8 +366,9 @@ int seg_train_step(seg_handle h, const seg_train_args* a, void* stream) {
     const bool riders = knob_i("SEG_STEP_RIDERS", 1) != 0;
     const long long v = h->out_vol();
     // every way out of the step (the optimiser has moved the parameters on: the workspace no longer belongs to a forward pass a caller could name)
-    struct RideGuard { seg_engine* e; ~RideGuard() { e->ride_on = false; e->ride_zero = nullptr; e->taps_fwd = e->taps_bwd = false; } } ride_guard{h};
+    struct RideGuard { seg_engine* e; ~RideGuard() { e->ride_on = false; e->ride_zero = nullptr; e->head_no_store = false; e->taps_fwd = e->taps_bwd = false; } } ride_guard{h};
     h->ride_on = riders; h->head_zeroed = false;
+    h->head_no_store = h->head_w_act >= 0;          // the backward pass of THIS step does not read the head's input: the forward pass does not write it
     h->ride_ingest = StepRider{}; h->ride_pack = StepRider{};
     if (riders) {
         if (a->mask_mode == SEG_MASKS_RANDOM) h->ride_ingest.bump = (int*)(h->ws + h->off_step);      // the dropout draw counter (after the mask kernel read it)
@@ -376,7 +379,7 @@ int seg_train_step(seg_handle h, const seg_train_args* a, void* stream) {
     }
     const int frc = seg_forward(h, a->x, a->mask_mode, a->masks, a->seed, a->logits, a->probs, stream);
     const bool zeroed = riders && h->head_zeroed;
-    h->ride_zero = nullptr;
+    h->ride_zero = nullptr; h->head_no_store = false;
     if (frc) { h->ride_on = false; return -1; }
     const double lbytes = (double)h->N * v * (4.0 * h->ncls + ((a->label_type & 15) == SEG_LABEL_U8 ? 1.0 : (a->label_type & 15) == SEG_LABEL_I64 ? 8.0 : 4.0));
     int pi = h->prof_begin(st, SEG_K_MISC, 2.0 * lbytes + 4.0 * h->N * v * h->ncls, 0.0);

@@ -56,6 +56,9 @@ struct Step {
     int stat_rep = 0;                         // replicas of the statistics buffers this unit's producers use (0 = STAT_REP)
     bool fold_fin = false;                    // statistics finalize folded into the consuming gn_act launch (no launch of its own)
     int x_fwd = -1, x_dg0 = -1, x_dg1 = -1;   // conv3x tiling of the forward / data-gradient launches (-1: conv3_kernel, row-major weights)
+    int head_w = 0;          // the GroupNorm-backward reduce pass of this unit also collects the head's weight gradient (GnHeadW): 1 the unit under the head (+ the
+                             // bias gradient), 2 the unit whose activation is that unit's residual; 0 no
+    size_t head_q = 0;       // ... its sums area (behind Q, cleared with it)
     int draw = -1;           // gradient wrt raw
     bool dual_dg = false;    // 1^d conv on a concat: both data-gradients come from one streaming launch (seg_conv_args.out1)
     bool rq_dg = false;      // ... and that launch also leaves the GroupNorm-backward sums of vact_unit (set together with rq_fused of the ACT step it reads)
@@ -134,6 +137,10 @@ struct seg_engine {
     bool dual_gn_bwd = true;    // SEG_DUAL_GN=0: one GroupNorm-backward pass per branch of the VNet input block
     bool use_rq_fuse = true;    // SEG_RQ_FUSE=0: the GroupNorm-backward reduction of a VNet up-conv unit as a launch of its own
     bool use_head_fuse = true;  // SEG_HEAD_FUSE=0: the 1^d head as a launch of its own
+    int use_head_wfuse = 1;     // SEG_HEAD_WFUSE=0: head_bwd_kernel reads the head's input for its weight gradient; 1: the GroupNorm-backward reduce passes under a
+                                // one-class head collect it where that input is >= 16 MB; 2: on small tensors too (tests)
+    int head_w_act = -1;        // plan: the ACT step that writes the head's input when the head's weight gradient is collected that way (-1: bwd_head computes it)
+    bool head_no_store = false; // seg_train_step with head_w_act >= 0: that activation pass does not write its tensor (nothing reads it any more)
     int use_vact = 1;           // SEG_VACT=0: the activation between a VNet up-conv and the 1^d conv on the concat is written as a tensor; 2: applied on load on small tensors too (tests)
     bool use_coop = true;       // SEG_GN_COOP=0: the deep levels' GroupNorm backward as reduce + apply launches (one-workgroup-per-group launch at 6^3)
     std::vector<hipEvent_t> ready_ev;

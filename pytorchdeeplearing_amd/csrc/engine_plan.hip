@@ -177,6 +177,7 @@ struct Builder {
             }
             prev = t;
         }
+        e.taps.push_back({"up_tr32", prev});      // the head's input (activation only: its gradient is virtual under a one-class head)
         head(prev, "out_tr.conv");
     }
 
@@ -534,7 +535,9 @@ void fwd_act(seg_engine& E, int si, hipStream_t st) {
         if (E.ride_on && E.ride_zero) { a.zero_ptr = E.ride_zero; a.zero_n = E.ride_zero_n; E.head_zeroed = true; }
     }
     const int pi = E.prof_begin(st, SEG_K_GN_ACT, E.tbytes(s.out) * (2 + (s.ub >= 0) + (s.res >= 0)), 0.0);
-    launch_gn_act(a, E.dtype, st);
+    // train step whose head gradient comes from the reduce passes: the head inside this pass was the tensor's last reader
+    const bool no_store = s.head_fused && E.head_no_store && si == E.head_w_act;
+    launch_gn_act(a, E.dtype, st, no_store);
     E.prof_end(st, pi);
 }
 
@@ -671,16 +674,23 @@ void bwd_act(seg_engine& E, int asi, int ui, const std::vector<int>& gl, hipStre
         E.prof_end(st, pg);
         return;
     }
+    // the head's weight / bias gradient collected by this pair (Planner::mark_head_wfuse)
+    GnHeadW hw{};
+    if (u.head_w) {
+        const Step& hs = E.steps[E.head_step];
+        hw.sums = (double*)(E.ws + u.head_q); hw.dw = E.g + E.params[hs.w].off; hw.db = E.g + E.params[hs.b].off;
+    }
+    const GnHeadW* hwp = u.head_w ? &hw : nullptr;
     if (E.steps[asi].rq_fused) a.rep_q = f.rep_q = 0;      // the sums came with the data-gradient launch that wrote dy[0], spread over all STAT_REP replicas
     else {
         const int pi = E.prof_begin(st, SEG_K_GN_BWD_REDUCE, E.tbytes(u.raw) * (a.ndy + 1), 0.0);
-        launch_gn_bwd_reduce(a, E.dtype, st);
+        launch_gn_bwd_reduce(a, E.dtype, st, hwp);
         E.prof_end(st, pi);
     }
     const bool fold = E.use_fold && a.C <= 256;
     if (!fold) launch_gn_bwd_finalize(f, st);
     const int pi = E.prof_begin(st, SEG_K_GN_BWD_APPLY, E.tbytes(u.raw) * (a.ndy + 2), 0.0);
-    launch_gn_bwd_apply(a, E.dtype, st, fold ? &f : nullptr, nullptr);
+    launch_gn_bwd_apply(a, E.dtype, st, fold ? &f : nullptr, nullptr, hwp);
     E.prof_end(st, pi);
 }
 
@@ -802,6 +812,7 @@ struct Planner {
         mark_fused_stem();
         mark_vact();
         mark_head_fuse();
+        mark_head_wfuse();
         mark_fold();
         layout_workspace();
         layout_packed_weights();
@@ -879,6 +890,53 @@ struct Planner {
         }
     }
 
+    // the GroupNorm backward of ACT step A is a gn_bwd_reduce_kernel + gn_bwd_apply_kernel pair that takes the virtual head source: one branch, a written
+    // tensor, not the fused input block, not the one-launch small-tensor form (the co-operative form never takes a virtual source, the sums on a data-gradient
+    // launch belong to never-written activations)
+    bool reduce_pass_under_head(const Step& A) const {
+        if (A.type != ST_ACT || A.ub >= 0 || A.vact) return false;
+        const Step& u = E.steps[A.ua];
+        return !u.fused_stem && u.gn_w >= 0 && !small_group(u);
+    }
+    int readers_of(int ten) const {
+        int n = 0;
+        for (auto& c : E.steps) {
+            if (c.type == ST_UNIT) n += (c.in0 == ten) + (c.in1 == ten);
+            else if (c.type == ST_ACT) n += c.res == ten;
+            else n += c.in == ten;
+        }
+        return n;
+    }
+
+    // ---- weight / bias gradient of a one-class head from the GroupNorm-backward reduce passes of the units its input is made of (GnHeadW): the head's input
+    // A.out = relu(GN(L)) [+ B.out], B.out = relu(GN(C)), is then read by nobody but the head's forward, and head_bwd_kernel (one launch, one pass over the
+    // tensor) goes.  Like mark_vact only where the tensor costs bandwidth, SEG_HEAD_WFUSE=2 anywhere.
+    void mark_head_wfuse() {
+        for (auto& s : E.steps) { s.head_w = 0; s.head_q = 0; }
+        E.head_w_act = -1;
+        if (!E.use_head_wfuse || !E.use_vhead) return;
+        for (auto& hs : E.steps) {
+            if (hs.type != ST_HEAD || hs.Cout != 1) continue;
+            for (size_t ai = 0; ai < E.steps.size(); ++ai) {
+                Step& A = E.steps[ai];
+                if (A.type != ST_ACT || A.out != hs.in || !reduce_pass_under_head(A)) continue;
+                const int C = E.tens[A.out].C;
+                if (C > 128 || readers_of(A.out) != 1) continue;
+                if (E.use_head_wfuse < 2 && (double)ten_bytes(E.tens[A.out]) < 16e6) continue;
+                Step* B = nullptr;
+                if (A.res >= 0) {
+                    for (auto& b : E.steps)
+                        if (b.type == ST_ACT && b.out == A.res) B = &b;
+                    // (two readers: A's residual and one conv - the virtual source plus ONE stored gradient)
+                    if (!B || B->res >= 0 || !reduce_pass_under_head(*B) || E.tens[B->out].C != C || readers_of(B->out) != 2) continue;
+                }
+                E.steps[A.ua].head_w = 1;
+                if (B) E.steps[B->ua].head_w = 2;
+                E.head_w_act = (int)ai;
+            }
+        }
+    }
+
     // ---- statistics finalize folded into the elementwise consumer (not for the fused input block / one-launch small tensors)
     void mark_fold() {
         for (auto& s : E.steps) s.fold_fin = false;
@@ -907,6 +965,8 @@ struct Planner {
         const size_t q0 = cur;
         for (auto& s : E.steps)
             if (s.type == ST_UNIT && s.gn_w >= 0) s.Q = alloc((size_t)STAT_REP * N * s.Cout * 2 * 8);
+        for (auto& s : E.steps)          // head weight-gradient sums: part of the Q region, so whatever clears Q clears them (only where the path is planned)
+            if (s.type == ST_UNIT && s.head_w) s.head_q = alloc((size_t)STAT_REP * N * s.Cout * 2 * 8);
         E.off_Q = q0; E.Q_bytes = cur - q0;
         for (auto& s : E.steps)
             if (s.type == ST_UNIT && s.gn_w >= 0) {
@@ -1059,6 +1119,7 @@ struct Planner {
             }
             if (!ok) return false;
         }
+        if (E.head_w_act >= 0 && E.head_din_needed) { g_err = "internal: the head's weight gradient rides on passes that do not take the virtual head source"; return false; }
         return true;
     }
     void plan_bwd_head(int si) {
@@ -1069,7 +1130,10 @@ struct Planner {
         E.head_din_needed = !E.use_vhead;
         E.head_step = si;
         E.tens[s.in].grads.push_back(gin);
-        push_bwd({s.w, s.b}, [e, si, gin](hipStream_t st) { bwd_head(*e, si, gin, st); });
+        // head_w_act: the op stays (the op numbering of a plan does not depend on the switch) but launches nothing - w / b finish with the last reduce + apply
+        // pair that collects them (plan_bwd_act)
+        if (E.head_w_act >= 0) push_bwd({}, [](hipStream_t) {});
+        else push_bwd({s.w, s.b}, [e, si, gin](hipStream_t st) { bwd_head(*e, si, gin, st); });
     }
     // the classification head opens the backward pass: its four parameters are registered last, so the finished gradients form a suffix from here on
     void plan_bwd_cls(int si) {
@@ -1121,7 +1185,14 @@ struct Planner {
             if (ui < 0) continue;
             Step& u = E.steps[ui];
             u.draw = new_grad(u.raw);
-            push_bwd({u.gn_w, u.gn_b, u.b}, [e, si, ui, gl](hipStream_t st) { bwd_act(*e, si, ui, gl, st); });      // gamma/beta and (analytically) the conv bias
+            std::vector<int> wr{u.gn_w, u.gn_b, u.b};          // gamma/beta and (analytically) the conv bias
+            if (u.head_w) {
+                // the head's w / b are complete behind the LATER of the passes that collect them (backward order: unit 1, then unit 2 where there is one)
+                bool later = false;
+                for (auto& o : E.steps) later |= o.type == ST_UNIT && o.head_w > u.head_w;
+                if (!later) { wr.push_back(E.steps[E.head_step].w); wr.push_back(E.steps[E.head_step].b); }
+            }
+            push_bwd(wr, [e, si, ui, gl](hipStream_t st) { bwd_act(*e, si, ui, gl, st); });
         }
         return true;
     }

@@ -138,6 +138,18 @@ __device__ __forceinline__ double gn_fold_sum_r(const GnBwdFinArgs& f, int n, in
     return r1;
 }
 
+// ---- head weight gradient collected by a reduce pass (GnHeadW): the fold of one sample, by the workgroup that publishes the sample's other gradients -------
+// h.Q: the sums area, shaped like Q - slot [c][0] = sum_v dl * activation[c], slot [0][1] = sum_v dl - over h.rep_q replicas; h.dgamma: the head's weight
+// gradient [C], h.dbias: its bias gradient or null (the pass that did not collect it).  C + 1 threads, no barrier.
+__device__ __forceinline__ void gn_head_w_fold(const GnBwdFinArgs& h, int n) {
+    const int tid = threadIdx.x, C = h.C;
+    if (tid > C || (tid == C && !h.dbias)) return;
+    const int c = tid < C ? tid : 0, which = tid < C ? 0 : 1;
+    double s = 0.0;
+    gn_fold_replicas<8, 1>(0, 1, h.rep_q > 0 ? h.rep_q : STAT_REP, &s, [&](int rep, double* v) { v[0] = h.Q[gn_rep_at(rep, h.N, n, C, c) + which]; });
+    atomicAdd(which ? h.dbias : &h.dgamma[c], (float)s);
+}
+
 // ---- the finalize of one sample inside a consumer workgroup (256 threads, C = 16..256) ---------------------------------------------------------------
 // Forward: fold the `rep` replica partial sums, reduce the channels of a group with lane butterflies (the cpg = C/8 channels of a group are
 // neighbouring lanes) and leave scale / shift of every channel in LDS.  `publish`: this workgroup also writes the per-(n, c) coefficients and

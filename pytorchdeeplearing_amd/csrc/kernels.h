@@ -170,7 +170,8 @@ struct ActArgs {
     const float* head_w = nullptr; const float* head_b = nullptr; float* logits = nullptr; float* probs = nullptr; int head_C = 0;
     double* zero_ptr = nullptr; long long zero_n = 0;
 };
-void launch_gn_act(const ActArgs& a, int dtype, hipStream_t s);
+// no_store (one-class head in the pass only): `out` is not written - logits / probabilities are the pass's only results (seg_train_step with GnHeadW below)
+void launch_gn_act(const ActArgs& a, int dtype, hipStream_t s, bool no_store = false);
 inline bool gn_act_head_supported(int C, int head_C, bool two_branches) { return C == 16 && !two_branches && (head_C == 1 || head_C == 2 || head_C == 4); }
 
 // GroupNorm+dropout+ReLU backward, pass 1: Q[n][c] = {sum dzr, sum dzr*r}, dzr = (sum_i dy_i)*[scale*r+shift>0]
@@ -191,10 +192,17 @@ struct GnBwdArgs {
     // back by every GroupNorm-backward pass it feeds
     const float* vdl; const float* vw; int vK;    int rep_q;                                  // replicas of Q the reduce pass spreads over; 0 = STAT_REP
 };
-void launch_gn_bwd_reduce(const GnBwdArgs& a, int dtype, hipStream_t s);
+// Weight / bias gradient of a ONE-class 1^d head without a pass of its own over the head's input: dW[c] = sum_v dl[v] * in[v][c], and the GroupNorm-backward
+// reduce passes of the units that make up `in` hold dl (their virtual source) and the unit's activation already.  in = relu(GN(L)) [+ xcat]: the pass of unit
+// L (no stored source) sums dl * relu(GN(L)) in fp32 and dl itself, the pass of the unit behind xcat (one stored source) dl * xcat as stored (rounded to T).
+// Both leave their sums in `sums` (shaped and spread like Q, zero at the launch); the apply launch of the same unit adds them to dw / db (fp32, +=).
+struct GnHeadW { double* sums; float* dw; float* db; };
+bool gn_head_w_supported(const GnBwdArgs& a);       // virtual source with vK == 1, one branch, 0 or 1 stored sources, C <= 128
+void launch_gn_bwd_reduce(const GnBwdArgs& a, int dtype, hipStream_t s, const GnHeadW* hw = nullptr);
 struct GnBwdFinArgs;
 // fa != null: the backward finalize of the branch(es) runs as a prologue of this launch (no gn_bwd_finalize launch before it)
-void launch_gn_bwd_apply(const GnBwdArgs& a, int dtype, hipStream_t s, const GnBwdFinArgs* fa = nullptr, const GnBwdFinArgs* fb = nullptr);
+void launch_gn_bwd_apply(const GnBwdArgs& a, int dtype, hipStream_t s, const GnBwdFinArgs* fa = nullptr, const GnBwdFinArgs* fb = nullptr,
+                         const GnHeadW* hw = nullptr);
 
 struct GnBwdFinArgs {
     const double* Q;       // [N][C][2]

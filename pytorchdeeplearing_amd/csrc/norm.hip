@@ -50,8 +50,13 @@ __global__ __launch_bounds__(64) void gn_finalize_kernel(GnFinArgs a0, GnFinArgs
 // HC > 0 (C == 16: two neighbouring lanes hold a voxel): the 1^d head on this activation in the same pass.  The even lane starts head_fwd_kernel's fmaf chain
 // (bias, channels 0 .. 7) on the values as stored, the odd lane continues it (channels 8 .. 15) and writes the voxel's logits / probabilities: same operations
 // in the same order as the separate launch.
-template <class T, bool FOLD, bool R2, bool RES, int HC = 0>
+// HCF = classes + 16 (GN_ACT_NO_STORE): the same pass without the store of `out` - the train step where the head was the tensor's only reader and its weight
+// gradient comes out of the GroupNorm-backward reduce passes (GnHeadW): 113 MB less written at 4 x 96^3.
+constexpr int GN_ACT_NO_STORE = 16;
+template <class T, bool FOLD, bool R2, bool RES, int HCF = 0>
 __global__ __launch_bounds__(256) void gn_act_kernel(ActArgs a) {
+    constexpr int HC = HCF & (GN_ACT_NO_STORE - 1);
+    constexpr bool STORE = HCF < GN_ACT_NO_STORE;
     __shared__ double part[FOLD ? 256 : 1][2];
     __shared__ float coef_s[FOLD ? 4 : 1][256];
     if (HC > 0 && a.zero_ptr && blockIdx.x == 0 && blockIdx.y == 0)
@@ -124,7 +129,7 @@ __global__ __launch_bounds__(256) void gn_act_kernel(ActArgs a) {
             vec<T, 8> o;
 #pragma unroll
             for (int j = 0; j < 8; ++j) o[j] = from_f<T>(y[j]);
-            if (ok[u]) store8(out + iu[u] * 8, o);
+            if (STORE && ok[u]) store8(out + iu[u] * 8, o);
             if constexpr (HC > 0) {
                 // (per_n is even and the trip stride a multiple of 256: both lanes of a voxel take the same trips)
                 const bool hi = threadIdx.x & 1;
@@ -201,9 +206,13 @@ __device__ __forceinline__ void load_dy_sum(const GnBwdArgs& a, long long i, flo
 // NDY = 4 / 5: the virtual head source of a one-class head (vK == 1: dy[v][c] += dl[n][v] * w[c]) plus 0 / 1 stored sources - the two
 // 96^3 units under the head, the largest GroupNorm-backward launches of the step; one scalar load per chunk, the head weights of the
 // thread's channels are loop-invariant (vw8, loaded by the caller)
+// NDY = 6 / 7: as 4 / 5, and the pass also forms the head's weight gradient (GnHeadW, kernels.h) from what it holds anyway - dl and the unit's activation:
+//   6 (the unit under the head, no stored source): sum_v dl * relu(GN(r)) per channel in fp32, and sum_v dl (the head's bias gradient)
+//   7 (the unit whose activation is that unit's residual, one stored source): sum_v dl * round_T(relu(GN(r))), the activation as gn_act_kernel stored it
 template <class T, int NDY> struct DySrc {
     static constexpr bool VH = NDY >= 4;
-    static constexpr int NS = VH ? NDY - 4 : NDY;
+    static constexpr bool HW = NDY >= 6;
+    static constexpr int NS = VH ? (NDY - 4) % 2 : NDY;
     vec<T, 8> d[NS > 0 ? NS : 1];
     float g0[8];
     float dl;
@@ -222,16 +231,28 @@ template <class T, int NDY> struct DySrc {
             for (int j = 0; j < 8; ++j) g[j] += to_f(d[k][j]);          // same order as load_dy_sum: ((head + d0) + d1) + d2
     }
 };
-__host__ inline int dy_variant(const GnBwdArgs& a) {
+__host__ inline int dy_variant(const GnBwdArgs& a, const GnHeadW* hw = nullptr) {
+    if (hw) {
+        if (!gn_head_w_supported(a)) { fprintf(stderr, "segengine: head weight gradient on a GroupNorm-backward pass: unsupported arguments (internal error)\n"); abort(); }
+        return 6 + a.ndy;
+    }
     if (a.vdl) return (a.vK == 1 && a.ndy >= 0 && a.ndy <= 1) ? 4 + a.ndy : 0;
     return (a.ndy >= 1 && a.ndy <= 3) ? a.ndy : 0;
 }
 
 // pass 1.  grid = (slabs, N); a block reduces `rows_per_block` voxels of one sample over all channels.
 // thread = (chunk column cc, row group g); LDS tree over row groups; fp64 atomics per (n,c).
+#ifndef SEG_EMU
+#define SEG_GNB_WAVES(x) __attribute__((amdgpu_waves_per_eu(x)))     // lower bound on resident waves per SIMD = upper bound on VGPRs
+#else
+#define SEG_GNB_WAVES(x)
+#endif
+// (NDY 6 / 7: nine more accumulators; left alone hipcc takes 130 - 136 registers for the 16-bit types, three waves per SIMD where NDY 4 has five.  Not for f32:
+// four rows of 32-byte chunks in flight do not fit 128 registers, <float, 7> would spill)
 template <class T, bool DUAL, int NDY>
-__global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(GnBwdArgs a, int GNB_ROWS) {
-    __shared__ float red[256 * 16];
+__global__ __launch_bounds__(256) SEG_GNB_WAVES(NDY >= 6 && sizeof(T) == 2 ? 4 : 1) void gn_bwd_reduce_kernel(GnBwdArgs a, int GNB_ROWS) {
+    constexpr int RS = NDY >= 6 ? 25 : 16;      // floats per thread in the LDS tree: q1, q2 (+ the head sums: 8 channels and dl)
+    __shared__ float red[256 * RS];
     const int tid = threadIdx.x, n = blockIdx.y;
     const int CPR = a.C / 8;                  // 2..32 (power of two)
     const int G = 256 / CPR;
@@ -256,6 +277,10 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(GnBwdArgs a, int GNB
 #pragma unroll
     for (int j = 0; j < 8; ++j) vw8[j] = 0.f;
     if (DySrc<T, NDY>::VH) vw8 = *(const vec<float, 8>*)(a.vw + cc * 8);
+    constexpr bool HW = DySrc<T, NDY>::HW;
+    float hw8[HW ? 8 : 1], hb = 0.f;          // head weight gradient of the thread's channels; sum of dl (used from the cc == 0 column)
+#pragma unroll
+    for (int j = 0; j < (HW ? 8 : 1); ++j) hw8[j] = 0.f;
     long long v = v0 + g;
     for (; v < v1; v += (long long)RW * G) {
         long long iu[RW];
@@ -291,22 +316,50 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(GnBwdArgs a, int GNB
                     p2[j] = fmaf(e, zv, p2[j]);
                 }
             }
+            if constexpr (HW) {
+                const float dlu = ok[u] ? src[u].dl : 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    float av = gn_relu(sc[j], to_f(x[u][j]), sh[j]);
+                    if (NDY == 7) av = to_f(from_f<T>(av));
+                    hw8[j] = fmaf(dlu, av, hw8[j]);
+                }
+                if (NDY == 6) hb += dlu;
+            }
         }
     }
 #pragma unroll                  // (unrolled: `br ? p1 : q1` under a run-time branch index sent all four accumulator arrays to scratch, 144 B per lane)
     for (int br = 0; br < (DUAL ? 2 : 1); ++br) {
         if (br) __syncthreads();
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { red[tid * 16 + j] = br ? p1[j] : q1[j]; red[tid * 16 + 8 + j] = br ? p2[j] : q2[j]; }
+        for (int j = 0; j < 8; ++j) { red[tid * RS + j] = br ? p1[j] : q1[j]; red[tid * RS + 8 + j] = br ? p2[j] : q2[j]; }
+        if constexpr (HW) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) red[tid * RS + 16 + j] = hw8[j];
+            red[tid * RS + 24] = hb;
+        }
         __syncthreads();
         // column (cc, j, which) summed over the G row groups by one thread each: CPR*16 <= 512 columns
         double* Q = br ? a.Q2 : a.Q;
         for (int col = tid; col < CPR * 16; col += 256) {
             const int ccx = col / 16, jj = col % 16;
             double s = 0.0;
-            for (int k = 0; k < G; ++k) s += red[(k * CPR + ccx) * 16 + jj];
+            for (int k = 0; k < G; ++k) s += red[(k * CPR + ccx) * RS + jj];
             const int c = ccx * 8 + (jj & 7), which = jj >> 3;
             atomicAdd(Q + (((long long)(blockIdx.x % (a.rep_q > 0 ? a.rep_q : STAT_REP)) * a.N + n) * a.C + c) * 2 + which, s);
+        }
+    }
+    if constexpr (HW) {
+        // the head sums take the same road, out of the same LDS pass (C + 1 <= 129 columns), into an area shaped like Q (a.Q2 of these variants:
+        // launch_gn_bwd_reduce), spread over the same replicas - not straight onto the head's gradient: a few thousand workgroups adding to 17 words would
+        // serialise.  Slot [c][0]: channel c; slot [0][1]: sum of dl (NDY 6 only).
+        const int col = 255 - tid;                                   // from the last wave down: those threads are idle in the loop above while C <= 64
+        if (col < CPR * 8 + (NDY == 6 ? 1 : 0)) {
+            const int ccx = col < CPR * 8 ? col / 8 : 0, jj = col < CPR * 8 ? 16 + col % 8 : 24;
+            double s = 0.0;
+            for (int k = 0; k < G; ++k) s += red[(k * CPR + ccx) * RS + jj];
+            const int c = jj < 24 ? ccx * 8 + (jj - 16) : 0, which = jj < 24 ? 0 : 1;
+            atomicAdd(a.Q2 + (((long long)(blockIdx.x % (a.rep_q > 0 ? a.rep_q : STAT_REP)) * a.N + n) * a.C + c) * 2 + which, s);
         }
     }
 }
@@ -392,6 +445,10 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(GnBwdArgs a, GnBwdFin
 #pragma unroll
             for (int j = 0; j < 8; ++j) { co2[j] = da[j]; co2[8 + j] = db[j]; co2[16 + j] = dc[j]; }
         }
+    }
+    // NDY 6 / 7 (never DUAL): fb describes the head sums the reduce launch left (launch_gn_bwd_apply); workgroup 0 of the sample adds them to the head's gradient
+    if constexpr (DySrc<T, NDY>::HW) {
+        if (blockIdx.x == 0) gn_head_w_fold(fb, n);
     }
     const vec<float, 8> sc = *(const vec<float, 8>*)(a.scale + (long long)n * a.C + c0);
     const vec<float, 8> sh = *(const vec<float, 8>*)(a.shift + (long long)n * a.C + c0);
@@ -734,20 +791,29 @@ void launch_gn_finalize(const GnFinArgs& a, hipStream_t s, const GnFinArgs* b) {
     hipLaunchKernelGGL(gn_finalize_kernel, dim3(GN_GROUPS, a.N, b ? 2 : 1), dim3(64), 0, s, a, b ? *b : a);
 }
 
-void launch_gn_act(const ActArgs& a, int dtype, hipStream_t s) {
+void launch_gn_act(const ActArgs& a, int dtype, hipStream_t s, bool no_store) {
     dim3 grid(ew_blocks_per_sample(a.V * (a.C / 8), a.fold != 0, a.N), a.N);
     if (a.head_w && !gn_act_head_supported(a.C, a.head_C, a.r2 != nullptr)) { fprintf(stderr, "segengine: head in the activation pass: unsupported shape (internal error)\n"); abort(); }
+    if (no_store && !(a.head_w && a.head_C == 1)) { fprintf(stderr, "segengine: activation pass without its store: one-class head only (internal error)\n"); abort(); }
     // HC: the head's classes computed in this pass (1, 2, else 4), 0 without a head; the head forms exist for one branch (no R2) only
-    const int hc = !a.head_w ? 0 : a.head_C == 1 ? 1 : a.head_C == 2 ? 2 : 4;
+    const int hc = !a.head_w ? 0 : no_store ? 1 + GN_ACT_NO_STORE : a.head_C == 1 ? 1 : a.head_C == 2 ? 2 : 4;
     by_dtype(dtype, [&](auto t) { by_bool(a.fold, [&](auto fold) { by_bool(a.r2 && !hc, [&](auto r2) { by_bool(a.res != nullptr, [&](auto rs) {
-        by_int<0, 1, 2, 4>(hc, [&](auto h) {
+        by_int<0, 1, 2, 4, 1 + GN_ACT_NO_STORE>(hc, [&](auto h) {
             if constexpr (!(r2() && h()))
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_act_kernel<tag_type<decltype(t)>, fold(), r2(), rs(), h()>), grid, dim3(256), 0, s, a);
         });
     }); }); }); });
 }
 
-void launch_gn_bwd_reduce(const GnBwdArgs& a, int dtype, hipStream_t s) {
+bool gn_head_w_supported(const GnBwdArgs& a) {
+    return a.vdl && a.vK == 1 && !a.r2 && a.ndy >= 0 && a.ndy <= 1 && a.C >= 16 && a.C <= 128;      // (the fold takes C + 1 threads of one wave quartet)
+}
+
+void launch_gn_bwd_reduce(const GnBwdArgs& a0, int dtype, hipStream_t s, const GnHeadW* hw) {
+    const int nv = dy_variant(a0, hw);
+    // head sums: the kernel argument block keeps its layout - the variants without a second branch find their area in its Q slot
+    GnBwdArgs a = a0;
+    if (hw) a.Q2 = hw->sums;
     // slab size: ~2048 workgroups in total, at least two rows per thread, at most 1024 rows (small tensors were
     // latency-bound with the fixed 512-row slabs: 16 workgroups x 16 serial round trips)
     const int G = 256 / (a.C / 8);
@@ -758,9 +824,9 @@ void launch_gn_bwd_reduce(const GnBwdArgs& a, int dtype, hipStream_t s) {
     if (rows > max_rows) rows = max_rows / G * G;
     const int GNB_ROWS = (int)rows;
     dim3 grid(cdiv(a.V, GNB_ROWS), a.N);
-    const int nv = dy_variant(a);
-    by_dtype(dtype, [&](auto t) { by_bool(a.r2 != nullptr, [&](auto dual) { by_int<1, 2, 3, 4, 5, 0>(nv, [&](auto k) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_bwd_reduce_kernel<tag_type<decltype(t)>, dual(), k()>), grid, dim3(256), 0, s, a, GNB_ROWS);
+    by_dtype(dtype, [&](auto t) { by_bool(a.r2 != nullptr, [&](auto dual) { by_int<1, 2, 3, 4, 5, 6, 7, 0>(nv, [&](auto k) {
+        if constexpr (!(dual() && k() >= 6))
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_bwd_reduce_kernel<tag_type<decltype(t)>, dual(), k()>), grid, dim3(256), 0, s, a, GNB_ROWS);
     }); }); });
 }
 
@@ -840,13 +906,20 @@ void launch_gn_bwd_finalize(const GnBwdFinArgs& a, hipStream_t s, const GnBwdFin
 }
 
 
-void launch_gn_bwd_apply(const GnBwdArgs& a, int dtype, hipStream_t s, const GnBwdFinArgs* fa, const GnBwdFinArgs* fb) {
+void launch_gn_bwd_apply(const GnBwdArgs& a, int dtype, hipStream_t s, const GnBwdFinArgs* fa, const GnBwdFinArgs* fb, const GnHeadW* hw) {
     const bool fold = fa != nullptr;
     dim3 grid(ew_blocks_per_sample(a.V * (a.C / 8), fold, a.N), a.N);
-    const GnBwdFinArgs za = fa ? *fa : GnBwdFinArgs{}, zb = fb ? *fb : GnBwdFinArgs{};
-    const int nv = dy_variant(a);
-    by_dtype(dtype, [&](auto t) { by_bool(a.r2 != nullptr, [&](auto dual) { by_bool(fold, [&](auto fd) { by_int<1, 2, 3, 4, 5, 0>(nv, [&](auto k) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_bwd_apply_kernel<tag_type<decltype(t)>, dual(), fd(), k()>), grid, dim3(256), 0, s, a, za, zb);
+    const GnBwdFinArgs za = fa ? *fa : GnBwdFinArgs{};
+    GnBwdFinArgs zb = fb ? *fb : GnBwdFinArgs{};
+    const int nv = dy_variant(a, hw);
+    if (hw) {          // the second branch's finalize block (these variants have none) carries the head sums: gn_head_w_fold
+        zb = GnBwdFinArgs{};
+        zb.Q = hw->sums; zb.dgamma = hw->dw; zb.dbias = a.ndy == 0 ? hw->db : nullptr;
+        zb.N = a.N; zb.C = a.C; zb.rep_q = a.rep_q;
+    }
+    by_dtype(dtype, [&](auto t) { by_bool(a.r2 != nullptr, [&](auto dual) { by_bool(fold, [&](auto fd) { by_int<1, 2, 3, 4, 5, 6, 7, 0>(nv, [&](auto k) {
+        if constexpr (!(dual() && k() >= 6))
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_bwd_apply_kernel<tag_type<decltype(t)>, dual(), fd(), k()>), grid, dim3(256), 0, s, a, za, zb);
     }); }); }); });
 }
 

@@ -441,11 +441,13 @@ def gn_forward(r1, stats1, gamma1, beta1, dtype, path, rep, mask1=None, r2=None,
     return o
 
 
-def gn_backward(dys, r, fwd, stats, gamma, dtype, path, rep_q, rep_s, mask=None, vdl=None, vw=None, second=None, bufs=None):
+def gn_backward(dys, r, fwd, stats, gamma, dtype, path, rep_q, rep_s, mask=None, vdl=None, vw=None, second=None, bufs=None, head=False):
     """Backward of gn_forward through the named path ("separate" | "fold" | "group" | "coop").  dys: list of 0..3 gradient tensors [N, V, C];
     vdl [N, K, V] / vw [K, C] fp32: the virtual head source; fwd: dict scale / shift / mean / rstd as the forward wrote them; second: dict
     r, scale, shift, mean, rstd, stats, gamma, mask of a second branch fed by the same sources.  Returns a dict: Q [32, N, C, 2], coef, dr, dgamma, dbeta,
-    dbias (and ...2).  bufs: output tensors to use instead of fresh zeroed ones (same keys)."""
+    dbias (and ...2).  bufs: output tensors to use instead of fresh zeroed ones (same keys).
+    head: the reduce launch also collects the weight / bias gradient of the one-class head behind the virtual source (seg_op_gn_backward_head):
+    head_dw [C], head_db [1] and the scratch head_sums [32, N, C, 2] join the dict."""
     lib = _capi.lib_for(r.device)
     N, V, C_ = r.shape
     o = dict(bufs or {})
@@ -475,6 +477,13 @@ def gn_backward(dys, r, fwd, stats, gamma, dtype, path, rep_q, rep_s, mask=None,
         setattr(a, k, _ptr(o[k]))
         setattr(a, k + "2", _ptr(o.get(k + "2")))
     a.N, a.C, a.V, a.rep_q, a.rep_s, a.path = N, C_, V, rep_q, rep_s, GN_BWD_PATH.get(path, path)
+    if head:
+        o.setdefault("head_sums", _alloc((32, N, C_, 2), torch.float64, r.device, zero=True))
+        o.setdefault("head_dw", _alloc((C_,), torch.float32, r.device, zero=True))
+        o.setdefault("head_db", _alloc((1,), torch.float32, r.device, zero=True))
+        lib.check(lib.seg_op_gn_backward_head(C.byref(a), _ptr(o["head_sums"]), _ptr(o["head_dw"]), _ptr(o["head_db"]), _capi.DTYPE[dtype],
+                                              _capi.stream_for(r.device)), "seg_op_gn_backward_head")
+        return o
     lib.check(lib.seg_op_gn_backward(C.byref(a), _capi.DTYPE[dtype], _capi.stream_for(r.device)), "seg_op_gn_backward")
     return o
 
