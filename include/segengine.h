@@ -15,6 +15,9 @@
  *   SEG_WGRAD_STREAM=0   weight gradients on the caller's stream instead of the library's second (low-priority) stream
  *   SEG_CONV3X=0         16-bit halo convolutions through conv3_kernel (round 1) instead of c3x::conv3x_kernel - bit-identical results
  *   SEG_STEMX=0          separate image-stem / GroupNorm / stem weight-gradient kernels instead of the fused input block
+ *   SEG_STEMX_ONEPASS=0|2 (read per seg_create) backward of the fused input block: 0 = two passes over the gradient sources (reduce; apply + stem weight
+ *                        gradients); otherwise ONE pass collects the GroupNorm sums and the coefficient-free moments of the stem weight gradients, and a
+ *                        combine launch behind the finalize applies the coefficients in fp64 - default where a gradient source is >= 16 MB, 2 = at every size
  *   SEG_VHEAD=0          the head writes its data-gradient tensor instead of the on-the-fly form
  *   SEG_GN_FOLD=0        GroupNorm finalize as launches of its own;  SEG_DUAL_GN=0: one GroupNorm-backward pass per branch of the VNet input block
  *   SEG_GN_COOP=0        (read per seg_create) GroupNorm backward of the >= 64-channel levels as reduce + apply launches instead of the one-launch
@@ -118,7 +121,8 @@ int seg_set_dropout_draws(seg_handle h, long long draws);
 int seg_plan(seg_handle h, int n, int d, int hgt, int wid);
 long long seg_workspace_bytes(seg_handle h);
 /* what the planner decided for the current shape (tests / diagnostics): what = 1: convolution units, 2: fork events the last backward pass recorded
- * on the caller's stream, 3: 1 where the head's weight gradient comes out of the GroupNorm-backward reduce passes (SEG_HEAD_WFUSE), else 0.
+ * on the caller's stream, 3: 1 where the head's weight gradient comes out of the GroupNorm-backward reduce passes (SEG_HEAD_WFUSE), else 0, 4: 1 where the backward of the fused
+ * input block reads its gradient sources once (SEG_STEMX_ONEPASS), else 0.
  * <0: not planned / unknown `what`. */
 int seg_plan_count(seg_handle h, int what);
 
@@ -436,6 +440,11 @@ int seg_op_wgrad3_cat(const void* dr, const void* x0, const void* x1, int c0, fl
  * mode 2: Q3 / Q1 ([32][N][16][2]: sum dz, sum dz*r with dz = (sum of the ndy gradient sources) * [scale*r + shift > 0]);
  * mode 3: weight gradients: d(raw) = coef[0]*dz + coef[1]*r + coef[2] (coef [N][16][3]) times the im2col rows, accumulated
  *         into dw3 (16, Cimg, 3^d) / dw1 (16, Cimg, 1^d) through `partial` (seg_op_stemx_partial_bytes of scratch).
+ * mode 4: mode 2's Q3 / Q1 plus, in the same pass, the per-workgroup moments of the weight gradients in `partial` (seg_op_stemx_moment_bytes of
+ *         scratch; a workgroup stays inside one sample): T1 = sum patch*dz, T2 = sum patch*r, T3 = sum patch over the valid voxels (fp32);
+ * mode 5: the combine: dw3 / dw1 += sum_n coef[n][co][0]*T1 + coef[n][co][1]*T2 + coef[n][co][2]*T3 from mode 4's `partial`, folded in fp64 in a fixed
+ *         order (takes coef3 / coef1, partial, the shape and w1 != NULL for two branches; modes 4 + 5 replace modes 2 + 3 - dz instead of d(raw) is
+ *         rounded to the run dtype, so the two are equal up to rounding, and exactly equal on data whose products and sums are exact).
  * w3 / w1: run-dtype [16][32] rows, k = tap*Cimg + ci / k = ci (seg_op_pack "conv_fwd" layout).  img: run dtype, channels-last. */
 typedef struct seg_stemx_args {
     const void* img; const void* w3; const void* w1;
@@ -450,6 +459,7 @@ typedef struct seg_stemx_args {
     int N, D, H, W, Cimg;
 } seg_stemx_args;
 long long seg_op_stemx_partial_bytes(int ndim, int n, int d, int h, int wid, int cimg);
+long long seg_op_stemx_moment_bytes(int ndim, int n, int d, int h, int wid, int cimg);
 int seg_op_stemx(const seg_stemx_args* a, int mode, int ndim, int dtype, float* dw3, float* dw1, void* stream);
 /* Register-blocked halo conv for 16-bit tensors with Cin % 32 == 0 or Cin == 16 (csrc/conv3x.hip): same operator as seg_op_conv3, the
  * weights packed with seg_pack_desc.frag = seg_op_conv3x_cfg_frag(cfg) (1; Cin == 16: 2 or 3) ("conv_fwd" / "conv_dgrad" element order), `in1` an optional second source of a
@@ -461,7 +471,7 @@ int seg_op_conv3x_num_cfgs(void);
 /* index in [0, num_cfgs): tiling id, ndim, box {d,h,w}, output channels per workgroup, resident 32-channel chunks, description */
 int seg_op_conv3x_cfg_info(int index, int* id, int* ndim, int* box3, int* bn, int* nres, char* name, int name_cap);
 int seg_op_conv3x_default_cfg(int ndim, int n, int d, int h, int wid, int cin, int cout, int dtype);
-/* seg_pack_desc.frag of the weights tiling `cfg` reads: 1, 2 (Cin == 16) or 3 (Cin == 16, 3-D tilings 28 .. 31: the halo fragments are reused across
+/* seg_pack_desc.frag of the weights tiling `cfg` reads: 1, 2 (Cin == 16) or 3 (Cin == 16, 3-D tilings 28 .. 29: the halo fragments are reused across
  * the kh taps, csrc/conv3x_impl.h conv3x16r_kernel); 0 for an unknown id */
 int seg_op_conv3x_cfg_frag(int cfg);
 /* sizeof of the structs of this header as compiled into the library: 0 conv, 1 wgrad, 2 pack, 3 stemx, 4 train, 5 gn_fwd, 6 gn_bwd */

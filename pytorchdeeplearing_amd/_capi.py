@@ -93,6 +93,7 @@ SIGNATURES = {
     "seg_op_wgrad3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "seg_op_wgrad3_cat": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "seg_op_stemx_partial_bytes": (_ll, [_i, _i, _i, _i, _i, _i]),
+    "seg_op_stemx_moment_bytes": (_ll, [_i, _i, _i, _i, _i, _i]),
     "seg_op_stemx": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "seg_abi_sizeof": (_i, [_i]),
     "seg_op_gn_forward": (_i, [_vp, _i, _vp]),

@@ -408,18 +408,24 @@ int seg_op_wgrad3_cat(const void* dr, const void* x0, const void* x1, int c0, fl
 long long seg_op_stemx_partial_bytes(int ndim, int n, int d, int h, int wid, int cimg) {
     return (long long)stemx_partial_bytes(ndim, n, ndim == 3 ? d : 1, h, wid, cimg);
 }
+long long seg_op_stemx_moment_bytes(int ndim, int n, int d, int h, int wid, int cimg) {
+    if (n < 1 || cimg < 1) return 0;
+    return (long long)stemx_moment_bytes(ndim, n, ndim == 3 ? d : 1, h, wid, cimg);
+}
 int seg_op_stemx(const seg_stemx_args* a, int mode, int ndim, int dtype, float* dw3, float* dw1, void* stream) {
     if (!a || !a->img || !a->w3) return fail("seg_op_stemx: null pointer");
-    if (mode < 0 || mode > 3) return fail("seg_op_stemx: mode must be 0..3");
+    if (mode < 0 || mode > 5) return fail("seg_op_stemx: mode must be 0..5");
+    if (a->N < 1) return fail("seg_op_stemx: batch must be >= 1");
     if (ndim != 2 && ndim != 3) return fail("seg_op_stemx: ndim must be 2 or 3");
     if (a->Cimg < 1 || a->Cimg > 3 || (ndim == 3 && a->Cimg != 1)) return fail("seg_op_stemx: image channels must be 1 (3-D) or 1..3 (2-D)");
     if ((long long)(ndim == 3 ? a->D : 1) * a->H * a->W * 16 * 4 >= (1ll << 31)) return fail("seg_op_stemx: volume too large for one buffer range");
     if (mode == 0 && (!a->stats3 || (a->w1 && !a->stats1))) return fail("seg_op_stemx: statistics pointers");
-    if (mode >= 1 && (!a->scale3 || !a->shift3 || (a->w1 && (!a->scale1 || !a->shift1)))) return fail("seg_op_stemx: scale / shift pointers");
+    if (mode >= 1 && mode != 5 && (!a->scale3 || !a->shift3 || (a->w1 && (!a->scale1 || !a->shift1)))) return fail("seg_op_stemx: scale / shift pointers");
     if (mode == 1 && !a->out) return fail("seg_op_stemx: out is null");
-    if (mode >= 2 && (a->ndy < 1 || a->ndy > 3 || !a->dy[0])) return fail("seg_op_stemx: gradient sources");
-    if (mode == 2 && (!a->Q3 || (a->w1 && !a->Q1))) return fail("seg_op_stemx: Q pointers");
-    if (mode == 3 && (!a->coef3 || (a->w1 && !a->coef1) || !a->partial || !dw3 || (a->w1 && !dw1))) return fail("seg_op_stemx: weight-gradient pointers");
+    if (mode >= 2 && mode != 5 && (a->ndy < 1 || a->ndy > 3 || !a->dy[0])) return fail("seg_op_stemx: gradient sources");
+    if ((mode == 2 || mode == 4) && (!a->Q3 || (a->w1 && !a->Q1))) return fail("seg_op_stemx: Q pointers");
+    if (mode == 4 && !a->partial) return fail("seg_op_stemx: moment scratch is null");
+    if ((mode == 3 || mode == 5) && (!a->coef3 || (a->w1 && !a->coef1) || !a->partial || !dw3 || (a->w1 && !dw1))) return fail("seg_op_stemx: weight-gradient pointers");
     launch_stemx(*a, mode, ndim, dtype, dw3, dw1, (hipStream_t)stream);
     return SEG_OK("seg_op_stemx");
 }

@@ -39,6 +39,7 @@ int seg_create(int net_kind, int ndim, int in_channels, int num_class, int init_
     e->use_vact = knob_i("SEG_VACT", e->use_vact);
     e->use_head_fuse = knob_i("SEG_HEAD_FUSE", e->use_head_fuse) != 0;
     e->use_head_wfuse = knob_i("SEG_HEAD_WFUSE", e->use_head_wfuse);
+    e->use_stemx_onepass = knob_i("SEG_STEMX_ONEPASS", e->use_stemx_onepass);
     e->use_rq_fuse = knob_i("SEG_RQ_FUSE", e->use_rq_fuse) != 0;
 #ifdef SEG_DIAG
     e->w3_mode = knob_i("SEG_DIAG_W3_MODE", e->w3_mode);
@@ -116,6 +117,7 @@ int seg_plan_count(seg_handle h, int what) {
     if (!h || !h->planned) return -1;
     if (what == 2) return h->n_event_forks;             // last backward pass: fork events recorded on the main stream
     if (what == 3) return h->head_w_act >= 0 ? 1 : 0;   // the head's weight gradient comes out of the GroupNorm-backward reduce passes (SEG_HEAD_WFUSE)
+    if (what == 4) return h->stem_onepass ? 1 : 0;      // the fused input block's backward reads its gradient sources once (SEG_STEMX_ONEPASS)
     int n = 0;
     for (auto& s : h->steps) {
         if (what == 1) n += s.type == ST_UNIT;                                            // convolution units

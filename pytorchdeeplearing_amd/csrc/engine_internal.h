@@ -133,6 +133,9 @@ struct seg_engine {
     int head_step = -1;
     bool use_stemx = true;      // SEG_STEMX=0: separate stem / GroupNorm / stem weight-gradient kernels (round-1 path)
     size_t off_partial_stemx = 0;
+    int use_stemx_onepass = 1;  // SEG_STEMX_ONEPASS=0: the fused input block's backward reads its gradient sources twice (reduce, apply); 1: once where a source
+                                // is >= 16 MB (the moments of the stem weight gradients ride on the reduce pass); 2: on small tensors too (tests)
+    bool stem_onepass = false;  // plan: the one-pass form is used (off_partial_stemx then holds stemx_moment_bytes)
     bool use_conv3x = true;     // SEG_CONV3X=0: conv3_kernel for every halo conv (round-1 path)
     bool dual_gn_bwd = true;    // SEG_DUAL_GN=0: one GroupNorm-backward pass per branch of the VNet input block
     bool use_rq_fuse = true;    // SEG_RQ_FUSE=0: the GroupNorm-backward reduction of a VNet up-conv unit as a launch of its own

@@ -614,7 +614,8 @@ void bwd_pool(seg_engine& E, int si, int gin, int gout, hipStream_t st) {
     launch_maxpool_bwd(a, E.dtype, st);
 }
 
-// fused input block: reduce (recomputing r), finalize per branch, then d(raw) in registers -> stem weight gradients
+// fused input block: reduce (recomputing r), finalize per branch, then d(raw) in registers -> stem weight gradients; planned as one pass
+// (Planner::mark_fused_stem): the reduce pass also collects the moments of the weight gradients, and a combine launch applies the coefficients
 void bwd_act_stem(seg_engine& E, int si, const std::vector<int>& gl, hipStream_t st) {
     const Step& s = E.steps[si];
     seg_stemx_args x = stemx_args(E, s);
@@ -622,16 +623,23 @@ void bwd_act_stem(seg_engine& E, int si, const std::vector<int>& gl, hipStream_t
     for (int i = 0; i < x.ndy; ++i) x.dy[i] = E.ws + E.tens[gl[i]].off;
     E.flush_side(st);
     const double tb = E.tbytes(s.out);
+    float* const dw3 = E.g + E.params[E.steps[s.ua].w].off;
+    float* const dw1 = s.ub >= 0 ? E.g + E.params[E.steps[s.ub].w].off : nullptr;
     int pi = E.prof_begin(st, SEG_K_STEM, tb * x.ndy, 0.0);
-    launch_stemx(x, 2, E.ndim, E.dtype, nullptr, nullptr, st);
-    E.prof_end(st, pi);
+    launch_stemx(x, E.stem_onepass ? 4 : 2, E.ndim, E.dtype, nullptr, nullptr, st);
+    if (!E.stem_onepass) E.prof_end(st, pi);
     const GnBwdFinArgs fa = gn_bwd_fin_args(E, E.steps[s.ua]);
     if (s.ub >= 0) {
         const GnBwdFinArgs fb = gn_bwd_fin_args(E, E.steps[s.ub]);
         launch_gn_bwd_finalize(fa, st, &fb);  // both branches: one launch
     } else launch_gn_bwd_finalize(fa, st);
+    if (E.stem_onepass) {
+        launch_stemx(x, 5, E.ndim, E.dtype, dw3, dw1, st);
+        E.prof_end(st, pi);
+        return;
+    }
     pi = E.prof_begin(st, SEG_K_STEM, tb * x.ndy, 0.0);
-    launch_stemx(x, 3, E.ndim, E.dtype, E.g + E.params[E.steps[s.ua].w].off, s.ub >= 0 ? E.g + E.params[E.steps[s.ub].w].off : nullptr, st);
+    launch_stemx(x, 3, E.ndim, E.dtype, dw3, dw1, st);
     E.prof_end(st, pi);
 }
 
@@ -839,12 +847,15 @@ struct Planner {
     // ---- fused input block: an ACT whose unit(s) are image stems (3^d [+ 1^d]) without a residual
     void mark_fused_stem() {
         for (auto& s : E.steps) s.fused_stem = false;
+        E.stem_onepass = false;
         if (!(E.use_stemx && E.feat == 16 && (long long)E.vol(0) * 16 * 4 < (1ll << 31))) return;
         for (auto& A : E.steps)
             if (A.type == ST_ACT && A.res < 0 && E.steps[A.ua].ck == CK_STEM3 && E.steps[A.ua].gn_w >= 0 &&
                 (A.ub < 0 || (E.steps[A.ub].ck == CK_STEM1 && E.steps[A.ub].gn_w >= 0))) {
                 E.steps[A.ua].fused_stem = true;
                 if (A.ub >= 0) E.steps[A.ub].fused_stem = true;
+                // the backward pass reads the gradient sources (tensors of A.out's size) once - like mark_vact where they cost bandwidth, SEG_STEMX_ONEPASS=2 anywhere
+                if (E.use_stemx_onepass && (E.use_stemx_onepass >= 2 || (double)ten_bytes(E.tens[A.out]) >= 16e6)) E.stem_onepass = true;
             }
     }
 
@@ -1079,7 +1090,7 @@ struct Planner {
         // halo weight gradients keep one partial-tile slot per layer until the reduce of their level visit (seg_engine::w3_slot)
         E.partial3_stride = align_up(p3);
         E.off_partial3 = alloc(E.partial3_stride * W3_BATCH);
-        E.off_partial_stemx = alloc(stemx_partial_bytes(E.ndim, N, d0, h0, w0, E.in_ch));
+        E.off_partial_stemx = alloc(E.stem_onepass ? stemx_moment_bytes(E.ndim, N, d0, h0, w0, E.in_ch) : stemx_partial_bytes(E.ndim, N, d0, h0, w0, E.in_ch));
         E.off_partial_stem1 = alloc(stem_wgrad_partial_bytes(E.ndim, N, d0, h0, w0, 16 * ((E.feat + 15) / 16)));
     }
 

@@ -36,9 +36,11 @@ bool launch_conv3x(int cfg, const void* in0, const void* in1, int C0, const void
 // replicas a statistics producer spreads its atomics over, by voxels per sample: enough to keep same-address fp64 atomics apart,
 // few enough that the consumer-side fold (gn_fold_block) reads ~8 KB
 inline int stat_rep_for(long long V) { return V >= 262144 ? 32 : V >= 65536 ? 16 : V >= 8192 ? 8 : 4; }
-// fused input block (stemx.hip): modes 0 forward statistics, 1 forward apply, 2 backward reduce, 3 backward apply + weight gradients
+// fused input block (stemx.hip): modes 0 forward statistics, 1 forward apply, 2 backward reduce, 3 backward apply + weight gradients,
+// 4 backward reduce + weight-gradient moments in one pass (stemx_moment_bytes of `partial`), 5 its combine (coefficients x moments -> dw3 / dw1)
 int stemx_workgroups(int ndim, int N, int D, int H, int W);
 size_t stemx_partial_bytes(int ndim, int N, int D, int H, int W, int Cimg);
+size_t stemx_moment_bytes(int ndim, int N, int D, int H, int W, int Cimg);
 void launch_stemx(const seg_stemx_args& a, int mode, int ndim, int dtype, float* dw3, float* dw1, hipStream_t s);
 int wgrad3_blocks_per_combo(int ndim, int N, int D, int H, int W, int P, int Q, int esz = 2);
 size_t wgrad3_partial_bytes(int ndim, int N, int D, int H, int W, int P, int Q);

@@ -8,6 +8,9 @@
 //   backward  SX_BWD_REDUCE  recompute r, Q = {sum dz, sum dz*r} per (n, c) and branch             (gradient sources + image)
 //             SX_BWD_APPLY   recompute r, d(raw) = A*dz + B*r + C in registers, and feed it as the B operand of a K = 16 MFMA
 //                            against the transposed im2col tile: the stem weight gradients without any d(raw) tensor
+//             SX_BWD_ONEPASS the reduce pass that also contracts the transposed im2col tile with dz, r and a ones column: A, B, C are
+//                            constant per (sample, channel), so dW = sum_n A*T1 + B*T2 + C*T3 needs only these coefficient-free moments
+//                            and the second read of the gradient sources goes (stemx_wgrad_reduce_kernel<true> applies the coefficients)
 // (gn_finalize / gn_bwd_finalize of norm.hip run between the passes, unchanged).
 // im2col without scalar gathers: the 1-channel halo is kept in LDS as three copies shifted by 0 / 1 / 2 elements, so the 16
 // voxels of an x row under any tap (kd, kh, kw) start 8-byte aligned in copy kw; ONE transposing read (ds_read_b64_tr_b16)
@@ -23,7 +26,10 @@
 namespace seg {
 namespace {
 
-enum { SX_FWD_STATS = 0, SX_FWD_APPLY = 1, SX_BWD_REDUCE = 2, SX_BWD_APPLY = 3 };
+enum { SX_FWD_STATS = 0, SX_FWD_APPLY = 1, SX_BWD_REDUCE = 2, SX_BWD_APPLY = 3, SX_BWD_ONEPASS = 4, SX_BWD_COMBINE = 5 };
+constexpr int SX_CAP = 2048;      // workgroups of one launch at the most
+constexpr int SX_ONEPASS_CAP = 1024;   // .. of SX_BWD_ONEPASS: two of its workgroups fit a CU (registers), so 1024 are two rounds of a 256-CU device; with 2048 the pass
+                                       // took 150 instead of 110 us at 4 x 96^3 and the moments were twice the bytes for the combine
 constexpr int SX_C = 16;          // output channels of the stems (init_features, fixed by seg_create)
 constexpr int SX_MAXCI = 3;       // image channels
 
@@ -38,12 +44,23 @@ template <int TD_, int TH_, int KD_> struct SBox {
     static __device__ __forceinline__ int tap_row(int tap) { return ((tap / 9) * HH + (tap / 3) % 3) * HWP; }   // (kd, kh) part of the halo offset
 };
 
+// SX_BWD_ONEPASS carries 32 accumulator registers more than the reduce pass: two waves per SIMD as its register budget (left alone hipcc interleaves the
+// tiles of a wave over 260 registers - one workgroup per CU; under the budget the 16-bit forms take 252 - 256 with 0 - 3 spilled registers); the other modes
+// keep the compiler's own choice (three waves in the 16-bit forms).  Tiles not interleaved (#pragma unroll 1): 194 registers, still two waves, 148 against
+// 122 us at 4 x 96^3.
+#ifndef SEG_EMU
+#define SEG_SX_WAVES(mode) __attribute__((amdgpu_waves_per_eu((mode) == SX_BWD_ONEPASS ? 2 : 1)))
+#else
+#define SEG_SX_WAVES(mode)
+#endif
+
 template <class T, class B, int MODE, int CIMG, int NDY>
-__global__ __launch_bounds__(256) void stemx_kernel(StemxArgs a) {
+__global__ __launch_bounds__(256) SEG_SX_WAVES(MODE) void stemx_kernel(StemxArgs a) {
     constexpr bool H16 = sizeof(T) == 2;
     constexpr int NCOPY = H16 ? 3 : 1;                            // shifted copies of every image-channel plane
     constexpr int TM = B::NTILE / 4;                              // tiles per wave
-    constexpr bool BWD = MODE == SX_BWD_REDUCE || MODE == SX_BWD_APPLY;
+    constexpr bool ONEPASS = MODE == SX_BWD_ONEPASS;
+    constexpr bool BWD = MODE == SX_BWD_REDUCE || MODE == SX_BWD_APPLY || ONEPASS;
     static_assert(B::NTILE % 4 == 0, "tiles must split over the four waves");
     constexpr int XELEMS = (CIMG * NCOPY + 1) * B::HVP;       // + one all-zero plane: the padding k slots (k >= K) read it at the tile's offset
     constexpr int DELEMS = BWD ? 2 * NDY * B::V * SX_C : 8;         // two buffers of NDY gradient-source tiles
@@ -101,9 +118,13 @@ __global__ __launch_bounds__(256) void stemx_kernel(StemxArgs a) {
     // running sums of this workgroup for the current sample (flushed when the sample changes): [branch][which]
     float acc_s[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
     f32x4 accW3[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}}, accW1 = f32x4{0.f, 0.f, 0.f, 0.f};
+    // SX_BWD_ONEPASS: the moments of this workgroup's sample, tile order of the partial: T1_3, T2_3, T3 (two M tiles each), then T1_1, T2_1 (centre-tap M tile)
+    f32x4 accM[ONEPASS ? 8 : 1];
+#pragma unroll
+    for (int t = 0; t < (ONEPASS ? 8 : 1); ++t) accM[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     int cur_n = -1;
     auto flush = [&](int n) {                          // non-swapped layout: lane co = l15; sums over the 4 q groups, then over the waves
-        if (MODE != SX_FWD_STATS && MODE != SX_BWD_REDUCE) return;
+        if (MODE != SX_FWD_STATS && MODE != SX_BWD_REDUCE && !ONEPASS) return;
         __syncthreads();
 #pragma unroll
         for (int br = 0; br < 2; ++br)
@@ -228,13 +249,20 @@ __global__ __launch_bounds__(256) void stemx_kernel(StemxArgs a) {
     Coefs cnext{};
     int cur = 0;
     BoxAt pnext{0, 0, 0, 0};
-    if ((int)blockIdx.x < nbox) {
-        pnext = box_at((int)blockIdx.x);
+    // boxes of this workgroup: b_first, b_first + b_step, .. < b_end.  One pass over every box of the launch - or, SX_BWD_ONEPASS (whose moments
+    // are per sample, launched with gridDim.x = N * wps), over the boxes of ONE sample
+    int b_first = blockIdx.x, b_step = gridDim.x, b_end = nbox;
+    if (ONEPASS) {
+        const int bps = nbz * nby * nbx, wps = (int)gridDim.x / a.N, n = (int)blockIdx.x / wps;
+        b_first = n * bps + (int)blockIdx.x % wps; b_step = wps; b_end = n < a.N ? (n + 1) * bps : 0;
+    }
+    if (b_first < b_end) {
+        pnext = box_at(b_first);
         load_img(pnext);
         if (BWD) issue_dy(pnext, 0);
         load_coefs(pnext.n, cnext);
     }
-    for (int b = blockIdx.x; b < nbox; b += gridDim.x) {
+    for (int b = b_first; b < b_end; b += b_step) {
         const BoxAt bp = pnext;                          // (computed one trip ago for the prefetch)
         const int x0 = bp.x0, y0 = bp.y0, z0 = bp.z0, n = bp.n;
         if (n != cur_n) { if (cur_n >= 0) flush(cur_n); cur_n = n; }
@@ -250,8 +278,8 @@ __global__ __launch_bounds__(256) void stemx_kernel(StemxArgs a) {
         wait_vmem();                                     // the gradient tiles and the coefficients of box b have landed
         const Coefs cc = cnext;                          // this box's coefficients (loaded behind its prefetch, one trip ago)
         __syncthreads();
-        if (b + (int)gridDim.x < nbox) {
-            pnext = box_at(b + (int)gridDim.x);
+        if (b + b_step < b_end) {
+            pnext = box_at(b + b_step);
             load_img(pnext);
             if (BWD) issue_dy(pnext, cur ^ 1);
             load_coefs(pnext.n, cnext);
@@ -352,13 +380,42 @@ __global__ __launch_bounds__(256) void stemx_kernel(StemxArgs a) {
                 da[r] = gn_gate(sc3, ra[r], sh3, dy[r]);
                 db[r] = gn_gate(sc1, rb[r], sh1, dy[r], nbr == 2);
             }
-            if (MODE == SX_BWD_REDUCE) {
+            if (MODE == SX_BWD_REDUCE || ONEPASS) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     if (ok[r]) {
                         acc_s[0][0] += da[r]; acc_s[0][1] = fmaf(da[r], ra[r], acc_s[0][1]);
                         acc_s[1][0] += db[r]; acc_s[1][1] = fmaf(db[r], rb[r], acc_s[1][1]);
                     }
+                if (!ONEPASS) continue;
+            }
+            if constexpr (ONEPASS) {
+                // B operands of the K = 16 steps (k = voxel 4q + r, n = channel l15): dz rounded to the run dtype, r (a run-dtype value already) and ones.
+                // A voxel outside the volume contributes nothing: its recomputed r is not zero (its dz is - out-of-range source tiles are copied as zeros)
+                typename Mma16<T>::frag z3, z1, r3, r1, on;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    z3[r] = from_f<T>(ok[r] ? da[r] : 0.f); z1[r] = from_f<T>(ok[r] ? db[r] : 0.f);
+                    r3[r] = from_f<T>(ok[r] ? ra[r] : 0.f); r1[r] = from_f<T>(ok[r] ? rb[r] : 0.f);
+                    on[r] = from_f<T>(ok[r] ? 1.f : 0.f);
+                }
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) {
+                    typename Mma16<T>::frag xa;
+                    if constexpr (H16) {
+                        xa = *(const typename Mma16<T>::frag*)(Xc + tb + offW[mt]);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) xa[j] = offW[mt] >= 0 ? Xc[tb + offW[mt] + j] : from_f<T>(0.f);
+                    }
+                    accM[0 + mt] = Mma16<T>::run(xa, z3, accM[0 + mt]);
+                    accM[2 + mt] = Mma16<T>::run(xa, r3, accM[2 + mt]);
+                    accM[4 + mt] = Mma16<T>::run(xa, on, accM[4 + mt]);
+                    if (mt == 0 && nbr == 2) {
+                        accM[6] = Mma16<T>::run(xa, z1, accM[6]);
+                        accM[7] = Mma16<T>::run(xa, r1, accM[7]);
+                    }
+                }
                 continue;
             }
             // SX_BWD_APPLY: d(raw) of this tile (rounded to the run dtype like the tensor it replaces) is the B operand of a K = 16
@@ -387,6 +444,35 @@ __global__ __launch_bounds__(256) void stemx_kernel(StemxArgs a) {
         else tiles(std::false_type{});
     }
     if (cur_n >= 0) flush(cur_n);
+    if constexpr (ONEPASS) {
+        // moment tiles of the four waves -> one partial per workgroup: [T1_3, T2_3: 2 x 16 x K | T3: K | T1_1, T2_1: 2 x 16 x K1].  The fold goes through the
+        // gradient-source buffer (nothing is in flight into it any more: the last trip issued no prefetch), as many tiles per pass as its smallest form holds
+        constexpr int TPP = (int)(DELEMS * sizeof(T) / (4 * 256 * sizeof(float))) < 8 ? (int)(DELEMS * sizeof(T) / (4 * 256 * sizeof(float))) : 8;
+        static_assert(TPP >= 1, "the gradient-source buffer holds one moment tile of every wave");
+        float* const fold = (float*)Dy;
+        const int K1 = nbr == 2 ? Cimg : 0;
+        float* dst = a.partial + (long long)blockIdx.x * (SX_C * 2 * (K + K1) + K);
+        const int ntile = nbr == 2 ? 8 : 6;
+        for (int t0 = 0; t0 < ntile; t0 += TPP) {
+            __syncthreads();                             // every wave is done with the source tiles / the previous pass
+#pragma unroll
+            for (int t = 0; t < 8; ++t)
+                if (t >= t0 && t < t0 + TPP && t < ntile) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) fold[((t - t0) * 4 + wv) * 256 + (4 * q + r) * 16 + l15] = accM[t][r];
+                }
+            __syncthreads();
+            for (int i = tid; i < TPP * 256; i += 256) {
+                const int t = t0 + i / 256, e = i % 256, kk = ((t < 6 && (t & 1)) ? 16 : 0) + e / 16, co = e % 16;      // tile t row e/16 = k slot
+                if (t >= ntile) break;
+                const float* f = fold + (i / 256) * 4 * 256 + e;
+                const float s = f[0] + f[256] + f[512] + f[768];
+                if (t < 4) { if (kk < K) dst[(t / 2) * SX_C * K + co * K + kk] = s; }
+                else if (t < 6) { if (kk < K && co == 0) dst[2 * SX_C * K + kk] = s; }
+                else if (kk >= kc0 && kk < kc0 + K1) dst[2 * SX_C * K + K + (t - 6) * SX_C * K1 + co * K1 + (kk - kc0)] = s;
+            }
+        }
+    }
     if (MODE == SX_BWD_APPLY) {
         // weight-gradient tiles of the four waves -> one partial per workgroup: [wg][branch 3: 16 x K | branch 1: 16 x Cimg]
         __syncthreads();
@@ -408,8 +494,49 @@ __global__ __launch_bounds__(256) void stemx_kernel(StemxArgs a) {
     }
 }
 
-// dw3[co][ci][tap] += sum_wg partial[wg][co][tap * Cimg + ci]; dw1[co][ci] likewise (PyTorch weight layouts)
-__global__ __launch_bounds__(256) void stemx_wgrad_reduce_kernel(const float* partial, float* dw3, float* dw1, int K, int K1, int Cimg, int ntap, int nwg) {
+// MOMENTS = false: dw3[co][ci][tap] += sum_wg partial[wg][co][tap * Cimg + ci]; dw1[co][ci] likewise (PyTorch weight layouts), partial tiles of SX_BWD_APPLY.
+// MOMENTS = true (the combine of SX_BWD_ONEPASS, one launch of 1024-thread workgroups): partial holds the moments of nwg = N * wps workgroups, wps consecutive
+// ones per sample;  dw[co][k] += sum_n A[n][co] * T1[n][co][k] + B[n][co] * T2[n][co][k] + C[n][co] * T3[n][k]  with (A, B, C) the coefficients
+// gn_bwd_finalize published.  grid = (16 weight elements, sample, half of the sample's workgroups): the launch is a read of N * wps * 3.7 KB in 64-byte pieces and
+// is bound by what ONE CU can request, so it is spread over as many CUs as the existing reduce (one launch of 28 workgroups took 39 us at 4 x 96^3, this one
+// 8 - 11 us).  Inside a workgroup everything is fp64 and in a fixed order: thread (slice, element) walks its share of the workgroups in workgroup order and
+// applies the coefficients to its sums (the cancellation B * (T2 - mu * T3) happens here, in fp64); the 64 slices are folded by a butterfly inside the wave
+// and in wave order across the waves; the 2 N workgroup results of an element are added in fp32 like the partial tiles of the two-pass form.
+template <bool MOMENTS>
+__global__ __launch_bounds__(MOMENTS ? 1024 : 256) void stemx_wgrad_reduce_kernel(const float* partial, const float* coef3, const float* coef1, float* dw3, float* dw1,
+                                                                                  int K, int K1, int Cimg, int ntap, int nwg, int N) {
+    if constexpr (MOMENTS) {
+        __shared__ double fold[16][16];
+        const int tid = threadIdx.x, o = tid & 15, sl = tid >> 4, wv = tid >> 6;
+        const int per = SX_C * 2 * (K + K1) + K, nout = SX_C * (K + K1), i = blockIdx.x * 16 + o;
+        const int wps = nwg / N, half = (wps + 1) / 2, h0 = blockIdx.z * half, h1 = h0 + half < wps ? h0 + half : wps;
+        const int chunk = (half + 63) / 64, j0 = h0 + sl * chunk, j1 = j0 + chunk < h1 ? j0 + chunk : h1, n = blockIdx.y;
+        const bool act = i < nout, br1 = i >= SX_C * K;
+        const int j = br1 ? i - SX_C * K : i, Kb = br1 ? K1 : K, co = act ? j / Kb : 0, k = act ? j % Kb : 0;
+        // element offsets of T1, T2 (this branch, this (co, k)) and T3 (the 1^d branch sits on the centre tap's k slots) inside one partial
+        const int o1 = br1 ? 2 * SX_C * K + K + j : j, o2 = o1 + SX_C * Kb, o3 = 2 * SX_C * K + (br1 ? (ntap / 2) * Cimg + k : k);
+        const float* const cf = br1 ? coef1 : coef3;
+        double tot = 0.0;
+        if (act) {
+            double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+            const float* p = partial + ((long long)n * wps + j0) * per;
+#pragma unroll 8
+            for (int w = j0; w < j1; ++w, p += per) { s1 += (double)p[o1]; s2 += (double)p[o2]; s3 += (double)p[o3]; }
+            const float* c = cf + ((long long)n * SX_C + co) * 3;
+            tot = (double)c[0] * s1 + (double)c[1] * s2 + (double)c[2] * s3;
+        }
+        tot += __shfl_xor(tot, 16);
+        tot += __shfl_xor(tot, 32);
+        if ((tid & 63) < 16) fold[wv][o] = tot;
+        __syncthreads();
+        if (tid < 16 && act) {
+            double v = 0.0;
+            for (int w = 0; w < 16; ++w) v += fold[w][o];
+            if (!br1) atomicAdd(&dw3[((long long)co * Cimg + k % Cimg) * ntap + k / Cimg], (float)v);
+            else if (dw1) atomicAdd(&dw1[j], (float)v);                 // [co][ci], 1^d kernel
+        }
+        return;
+    }
     const int per = SX_C * (K + K1);
     const int b0 = blockIdx.y * 64, b1 = b0 + 64 < nwg ? b0 + 64 : nwg;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < per; i += gridDim.x * 256) {
@@ -431,10 +558,10 @@ __global__ __launch_bounds__(256) void stemx_wgrad_reduce_kernel(const float* pa
 template <class T, class B, int CIMG>
 void launch_mode(const StemxArgs& a, int mode, int nwg, hipStream_t s) {
     dim3 grid(nwg), block(256);
-    // the forward modes take no gradient sources (NDY = 0), the backward ones 1, 2 or (anything else) 3; any mode past SX_BWD_REDUCE is the backward apply
+    // the forward modes take no gradient sources (NDY = 0), the backward ones 1, 2 or (anything else) 3; any mode past SX_BWD_ONEPASS is the backward apply
     const bool fwd = mode == SX_FWD_STATS || mode == SX_FWD_APPLY;
-    const int m = fwd || mode == SX_BWD_REDUCE ? mode : SX_BWD_APPLY, nd = fwd ? 0 : a.ndy == 1 ? 1 : a.ndy == 2 ? 2 : 3;
-    by_int<SX_FWD_STATS, SX_FWD_APPLY, SX_BWD_REDUCE, SX_BWD_APPLY>(m, [&](auto md) { by_int<0, 1, 2, 3>(nd, [&](auto n) {
+    const int m = fwd || mode == SX_BWD_REDUCE || mode == SX_BWD_ONEPASS ? mode : SX_BWD_APPLY, nd = fwd ? 0 : a.ndy == 1 ? 1 : a.ndy == 2 ? 2 : 3;
+    by_int<SX_FWD_STATS, SX_FWD_APPLY, SX_BWD_REDUCE, SX_BWD_APPLY, SX_BWD_ONEPASS>(m, [&](auto md) { by_int<0, 1, 2, 3>(nd, [&](auto n) {
         if constexpr ((md() == SX_FWD_STATS || md() == SX_FWD_APPLY) == (n() == 0))
             hipLaunchKernelGGL(HIP_KERNEL_NAME(stemx_kernel<T, B, md(), CIMG, n()>), grid, block, 0, s, a);
     }); });
@@ -444,7 +571,7 @@ void launch_mode(const StemxArgs& a, int mode, int nwg, hipStream_t s) {
 template <class T, class B, int CIMG>
 void launch_fwd_mode(const StemxArgs& a, hipStream_t s) {
     const long long nb = (long long)a.N * ((a.D + B::TD - 1) / B::TD) * ((a.H + B::TH - 1) / B::TH) * ((a.W + 15) / 16);
-    dim3 grid((unsigned)(nb < 2048 ? nb : 2048)), block(256);
+    dim3 grid((unsigned)(nb < SX_CAP ? nb : SX_CAP)), block(256);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(stemx_kernel<T, B, SX_FWD_APPLY, CIMG, 0>), grid, block, 0, s, a);
 }
 
@@ -457,8 +584,17 @@ inline long long sx_boxes(int ndim, int N, int D, int H, int W) {
 
 int stemx_workgroups(int ndim, int N, int D, int H, int W) {
     const long long nb = sx_boxes(ndim, N, ndim == 3 ? D : 1, H, W);
-    constexpr int cap = 2048;
-    return (int)(nb < cap ? nb : cap);
+    return (int)(nb < SX_CAP ? nb : SX_CAP);
+}
+// SX_BWD_ONEPASS keeps a workgroup inside one sample: N * wps workgroups, workgroup j of a sample walks its boxes j, j + wps, ..
+int stemx_onepass_workgroups(int ndim, int N, int D, int H, int W) {
+    const long long bps = sx_boxes(ndim, 1, ndim == 3 ? D : 1, H, W);
+    const int wps = SX_ONEPASS_CAP / N > 1 ? SX_ONEPASS_CAP / N : 1;
+    return N * (int)(bps < wps ? bps : wps);
+}
+size_t stemx_moment_bytes(int ndim, int N, int D, int H, int W, int Cimg) {
+    const int K = (ndim == 3 ? 27 : 9) * Cimg;
+    return (size_t)stemx_onepass_workgroups(ndim, N, D, H, W) * (SX_C * 2 * (K + Cimg) + K) * sizeof(float);
 }
 size_t stemx_partial_bytes(int ndim, int N, int D, int H, int W, int Cimg) {
     const int K = (ndim == 3 ? 27 : 9) * Cimg;
@@ -468,7 +604,13 @@ size_t stemx_partial_bytes(int ndim, int N, int D, int H, int W, int Cimg) {
 void launch_stemx(const seg_stemx_args& a0, int mode, int ndim, int dtype, float* dw3, float* dw1, hipStream_t s) {
     StemxArgs a = a0;
     if (ndim != 3) a.D = 1;
-    const int nwg = stemx_workgroups(ndim, a.N, a.D, a.H, a.W);
+    const int nwg = mode >= SX_BWD_ONEPASS ? stemx_onepass_workgroups(ndim, a.N, a.D, a.H, a.W) : stemx_workgroups(ndim, a.N, a.D, a.H, a.W);
+    const int ntap = ndim == 3 ? 27 : 9, K = ntap * a.Cimg, K1 = a.w1 ? a.Cimg : 0;
+    if (mode == SX_BWD_COMBINE) {
+        hipLaunchKernelGGL(stemx_wgrad_reduce_kernel<true>, dim3((SX_C * (K + K1) + 15) / 16, a.N, 2), dim3(1024), 0, s, (const float*)a.partial, a.coef3, a.coef1, dw3,
+                           dw1, K, K1, a.Cimg, ntap, nwg, a.N);
+        return;
+    }
     if (ndim == 3 && mode == SX_FWD_APPLY) {
         // 4 x 8 x 16 boxes for the forward apply pass: 2.1 halo elements staged per voxel instead of 2.8, half the per-box bookkeeping (MI355X, 4 x 96^3: 46 -> 36 us;
         // the statistics pass keeps the small box - its accumulators take 131 + 36 registers on the large one, three workgroups per SIMD instead of six, 45 us either way)
@@ -482,10 +624,9 @@ void launch_stemx(const seg_stemx_args& a0, int mode, int ndim, int dtype, float
         else by_int<1, 2, 3>(a.Cimg == 1 ? 1 : a.Cimg == 2 ? 2 : 3, [&](auto c) { launch_mode<T, SBox<1, 16, 1>, c()>(a, mode, nwg, s); });
     });
     if (mode == SX_BWD_APPLY) {
-        const int ntap = ndim == 3 ? 27 : 9, K = ntap * a.Cimg, K1 = a.w1 ? a.Cimg : 0;
         const int per = SX_C * (K + K1);
-        hipLaunchKernelGGL(stemx_wgrad_reduce_kernel, dim3((per + 255) / 256, (nwg + 63) / 64), dim3(256), 0, s, (const float*)a.partial, dw3, dw1, K, K1,
-                           a.Cimg, ntap, nwg);
+        hipLaunchKernelGGL(stemx_wgrad_reduce_kernel<false>, dim3((per + 255) / 256, (nwg + 63) / 64), dim3(256), 0, s, (const float*)a.partial,
+                           (const float*)nullptr, (const float*)nullptr, dw3, dw1, K, K1, a.Cimg, ntap, nwg, a.N);
     }
 }
 

@@ -345,10 +345,11 @@ def conv3x(x, wfrag, dtype, ndim, cout, bias=None, want_stats=False, out=None, x
     return (out, stats.sum(0)) if want_stats else out
 
 
-def stemx(mode, img, w3p, dtype, ndim, w1p=None, bias3=None, bias1=None, scale=None, shift=None, dys=(), coef=None):
+def stemx(mode, img, w3p, dtype, ndim, w1p=None, bias3=None, bias1=None, scale=None, shift=None, dys=(), coef=None, partial=None):
     """Fused input block (csrc/stemx.hip).  img [N,D,H,W,Cimg] run dtype; w3p / w1p packed "conv_fwd" rows; scale / shift / coef:
     pairs (branch 3, branch 1) of fp32 [N,16] / [N,16,3] tensors.  Returns per mode:
-    0 -> (stats3, stats1) fp64 [N,16,2];  1 -> out [N,D,H,W,16];  2 -> (Q3, Q1) fp64 [N,16,2];  3 -> (dw3, dw1) fp32 PyTorch layout."""
+    0 -> (stats3, stats1) fp64 [N,16,2];  1 -> out [N,D,H,W,16];  2 -> (Q3, Q1) fp64 [N,16,2];  3 -> (dw3, dw1) fp32 PyTorch layout;
+    4 -> (Q3, Q1, partial): mode 2's sums and the weight-gradient moments of the same pass;  5 -> (dw3, dw1) from `partial` and coef (the combine)."""
     lib = _capi.lib_for(img.device)
     N, D, H, W, cimg = img.shape
     dev = img.device
@@ -375,15 +376,19 @@ def stemx(mode, img, w3p, dtype, ndim, w1p=None, bias3=None, bias1=None, scale=N
         out = _alloc((N, D, H, W, 16), TORCH_DTYPE[dtype], dev, zero=True)
         a.out = out.data_ptr()
         res = lambda: out
-    elif mode == 2:
+    elif mode in (2, 4):
         qs = [_alloc((32, N, 16, 2), torch.float64, dev, zero=True) for _ in range(2)]
         a.Q3, a.Q1 = qs[0].data_ptr(), qs[1].data_ptr()
         res = lambda: (qs[0].sum(0), qs[1].sum(0))
+        if mode == 4:
+            part = aligned_empty(lib.seg_op_stemx_moment_bytes(ndim, N, D, H, W, cimg), dev)
+            a.partial = part.data_ptr()
+            res = lambda: (qs[0].sum(0), qs[1].sum(0), part)
     else:
         a.coef3 = coef[0].data_ptr()
         if two:
             a.coef1 = coef[1].data_ptr()
-        part = aligned_empty(lib.seg_op_stemx_partial_bytes(ndim, N, D, H, W, cimg), dev)
+        part = partial if mode == 5 else aligned_empty(lib.seg_op_stemx_partial_bytes(ndim, N, D, H, W, cimg), dev)
         a.partial = part.data_ptr()
         keep.append(part)
         dw3 = _alloc((16, cimg) + (3,) * ndim, torch.float32, dev, zero=True)
