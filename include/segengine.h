@@ -260,6 +260,25 @@ int seg_op_normalize_percentile(const float* x, float* out, long long n, float q
 int seg_op_gather_patches(const float* vol, int d, int h, int w, const int* origins, int nb, int pd, int ph, int pw, float* out, void* stream);
 int seg_op_stitch_mask(const unsigned char* masks, const int* origins, int nb, int pd, int ph, int pw, unsigned char* out,
                        int d, int h, int w, void* stream);
+/* ---- sliding-window inference with blended probabilities.  A window entry is four int32 {z, y, x, flipbits} in device memory (bit 0
+ * mirrors z, bit 1 y, bit 2 x); the same window may be listed several times with different flip bits (mirror augmentation).  Below,
+ * (i, j, k) is a position inside a window in volume orientation and a primed index is p - 1 - index on a mirrored axis, index otherwise.
+ * seg_op_gather_windows: out[b][i'][j'][k'] = vol[z_b + i][y_b + j][x_b + k], pad_value where that voxel lies outside the volume (a window
+ * may overhang, e.g. a volume smaller than the patch along an axis); out is [nb][pd][ph][pw] fp32. */
+int seg_op_gather_windows(const float* vol, int d, int h, int w, const int* entries, int nb, int pd, int ph, int pw, float pad_value, float* out,
+                          void* stream);
+/* For every voxel (z, y, x) of the half-open box box_lo <= (z, y, x) < box_hi (host int[3] each, inside the volume; the caller passes the
+ * bounding box of the batch's windows clipped to the volume) and every entry b, in index order, whose window contains the voxel:
+ * acc[c][z][y][x] += w * probs[b][c][i'][j'][k'] for c < C and wsum[z][y][x] += w, with (i, j, k) = (z - z_b, y - y_b, x - x_b) and
+ * w = (wz[i] * wy[j]) * wx[k] in fp32 (wz / wy / wx: device fp32 importance vectors of pd / ph / pw elements).  probs is [nb][C][pd][ph][pw],
+ * acc [C][d][h][w] and wsum [d][h][w] fp32, zeroed by the caller before the first batch; voxels outside the box are not touched.  No
+ * atomics: the additions into a voxel happen in entry order, so equal calls give equal bits.  C <= 16. */
+int seg_op_blend_windows(const float* probs, const int* entries, int nb, int c, int pd, int ph, int pw, const float* wz, const float* wy,
+                         const float* wx, const int* box_lo, const int* box_hi, float* acc, float* wsum, int d, int h, int w, void* stream);
+/* acc [C][v], wsum [v] -> mask [v] uint8: C == 1: (acc / wsum > threshold) * scale; C > 1: the first arg-max over acc[c] (the common divisor
+ * does not move it).  probs_out (NULL or [C][v] fp32) = acc[c] / wsum.  A voxel with wsum == 0 gives mask 0 and probability 0. */
+int seg_op_blend_finalize(const float* acc, const float* wsum, int c, long long v, float threshold, int scale, unsigned char* mask,
+                          float* probs_out, void* stream);
 /* dice_coeff / iou_coeff / multiclass_* on probabilities (model/metric.py:146-215): out2 = {dice, iou} */
 int seg_metric(const float* probs, const void* target, int label_type, int n, int c, long long v,
                void* ws, float* out2, void* stream);

@@ -136,6 +136,9 @@ SIGNATURES = {
     "seg_op_normalize_percentile": (_i, [_vp, _vp, _ll, _f, _f, _vp, _vp]),
     "seg_op_gather_patches": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     "seg_op_stitch_mask": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
+    "seg_op_gather_windows": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
+    "seg_op_blend_windows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i), _vp, _vp, _i, _i, _i, _vp]),
+    "seg_op_blend_finalize": (_i, [_vp, _vp, _i, _ll, _f, _i, _vp, _vp, _vp]),
     "seg_set_rccl_comm": (_i, [_vp, _vp, _vp]),
     "seg_profile_enable": (_i, [_vp, C.c_uint]),
     "seg_profile_read": (_i, [_vp, _vp, _vp, _vp, _vp]),

@@ -168,6 +168,34 @@ int seg_op_stitch_mask(const unsigned char* masks, const int* origins, int nb, i
     launch_stitch_mask(masks, origins, nb, pd, ph, pw, out, d, h, w, (hipStream_t)stream);
     return SEG_OK("seg_op_stitch_mask");
 }
+int seg_op_gather_windows(const float* vol, int d, int h, int w, const int* entries, int nb, int pd, int ph, int pw, float pad_value, float* out,
+                          void* stream) {
+    if (!vol || !entries || !out) return fail("seg_op_gather_windows: null pointer");
+    if (d < 1 || h < 1 || w < 1) return fail("seg_op_gather_windows: empty volume");
+    if (nb < 1 || pd < 1 || ph < 1 || pw < 1) return fail("seg_op_gather_windows: empty window list");
+    launch_gather_windows(vol, d, h, w, entries, nb, pd, ph, pw, pad_value, out, (hipStream_t)stream);
+    return SEG_OK("seg_op_gather_windows");
+}
+int seg_op_blend_windows(const float* probs, const int* entries, int nb, int c, int pd, int ph, int pw, const float* wz, const float* wy,
+                         const float* wx, const int* box_lo, const int* box_hi, float* acc, float* wsum, int d, int h, int w, void* stream) {
+    if (!probs || !entries || !wz || !wy || !wx || !box_lo || !box_hi || !acc || !wsum) return fail("seg_op_blend_windows: null pointer");
+    if (d < 1 || h < 1 || w < 1) return fail("seg_op_blend_windows: empty volume");
+    if (nb < 1 || pd < 1 || ph < 1 || pw < 1) return fail("seg_op_blend_windows: empty window list");
+    if (c < 1 || c > 16) return fail("seg_op_blend_windows: classes must be 1..16");
+    const int dims[3] = {d, h, w};
+    for (int a = 0; a < 3; ++a)
+        if (box_lo[a] < 0 || box_hi[a] > dims[a] || box_lo[a] >= box_hi[a]) return fail("seg_op_blend_windows: the box must be non-empty and inside the volume");
+    launch_blend_windows(probs, entries, nb, c, pd, ph, pw, wz, wy, wx, box_lo, box_hi, acc, wsum, d, h, w, (hipStream_t)stream);
+    return SEG_OK("seg_op_blend_windows");
+}
+int seg_op_blend_finalize(const float* acc, const float* wsum, int c, long long v, float threshold, int scale, unsigned char* mask, float* probs_out,
+                          void* stream) {
+    if (!acc || !wsum || !mask) return fail("seg_op_blend_finalize: null pointer");
+    if (c < 1 || c > 16) return fail("seg_op_blend_finalize: classes must be 1..16");
+    if (v < 1 || scale < 0 || scale > 255) return fail("seg_op_blend_finalize: empty volume or scale outside 0..255");
+    launch_blend_finalize(acc, wsum, c, v, threshold, scale, mask, probs_out, (hipStream_t)stream);
+    return SEG_OK("seg_op_blend_finalize");
+}
 
 int seg_metric(const float* probs, const void* target, int label_type, int n, int c, long long v, void* ws, float* out2, void* stream) {
     if (!probs || !target || !ws || !out2) return fail("seg_metric: null pointer");

@@ -361,6 +361,13 @@ void launch_normalize_percentile(const float* x, float* out, long long n, float 
 void launch_gather_patches(const float* vol, int D, int H, int W, const int* origins, int nb, int pd, int ph, int pw, float* out, hipStream_t s);
 void launch_stitch_mask(const unsigned char* masks, const int* origins, int nb, int pd, int ph, int pw, unsigned char* out, int D, int H, int W,
                         hipStream_t s);
+// sliding-window inference with blended probabilities (sliding.hip); entries = nb x {z, y, x, flipbits} int32 on the device, box_lo / box_hi on the host
+void launch_gather_windows(const float* vol, int D, int H, int W, const int* entries, int nb, int pd, int ph, int pw, float pad_value, float* out,
+                           hipStream_t s);
+void launch_blend_windows(const float* probs, const int* entries, int nb, int C, int pd, int ph, int pw, const float* wz, const float* wy,
+                          const float* wx, const int* box_lo, const int* box_hi, float* acc, float* wsum, int D, int H, int W, hipStream_t s);
+void launch_blend_finalize(const float* acc, const float* wsum, int C, long long V, float threshold, int scale, unsigned char* mask, float* probs_out,
+                           hipStream_t s);
 
 void launch_mask(const float* probs, unsigned char* out, int N, int C, long long V, float threshold, int scale, hipStream_t s);
 

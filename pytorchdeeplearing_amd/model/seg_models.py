@@ -40,7 +40,7 @@ class _SegModel(object):
     _mask_scale = 255      # BinaryUNet3dModel.predict returns *1 (modelUnet.py:678)
     _norm3d = "meanstd"    # VNet wrappers z-score (modelVNet.py:681); UNet wrappers use percentile normalize
     augment = None         # an ImageDataGenerator3D: trainprocess transforms every TRAINING batch on the device (pytorchdeeplearing_amd/augment.py)
-    postprocess = None     # callable, device uint8 (D, H, W) -> device uint8 (D, H, W): the 3-D inference / inference_patch mask on the source grid passes
+    postprocess = None     # callable, device uint8 (D, H, W) -> device uint8 (D, H, W): the 3-D inference / inference_patch / inference_sliding mask on the source grid passes
                            # through it before it leaves the device, e.g. functools.partial(prepost.keep_largest_component) (None changes nothing)
 
     def _init(self, dims, image_channel, numclass, batch_size, loss_name, inference, model_path, use_cuda):
@@ -284,6 +284,47 @@ class _SegModel(object):
             final[:m[0], :m[1], :m[2]] = back[:m[0], :m[1], :m[2]]
             final = self._postprocessed(final).cpu().numpy().astype(arr.dtype)          # np.zeros_like(source array) (modelUnet.py:752)
         return self._like(image_sitk, final)
+
+    def inference_sliding(self, image, newSpacing=(0.5, 0.5, 0.5), spacing=None, overlap=0.5, blend="gaussian", mirror_axes=(), clip=None,
+                          return_probs=False):
+        """Whole-volume inference for any 3-D wrapper (not in the reference): resample to `newSpacing` (linear), normalise the way this
+        wrapper's `inference` does (or clip to `clip=(lo, hi)` + z-score), run the network over half-overlapping windows of the model's patch
+        shape in batches of `batch_size`, blend the class PROBABILITIES with a centre-weighted importance map (`blend`: "gaussian" or
+        "constant"; `mirror_axes`: mirror test-time augmentation along 0 = z, 1 = y, 2 = x), take the threshold / arg-max once on the blended
+        field, resample the mask back (nearest) onto the source grid and pass it through `postprocess`.  Input and output as `inference_patch`;
+        with return_probs also the blended probabilities (C, D, H, W) on the resampled grid, a device tensor."""
+        if self._ndim != 3:
+            raise AttributeError("inference_sliding is a 3-D method")
+        from .. import prepost as PP
+        arr, src_spacing, image_sitk = self._volume_of(image, spacing)
+        patch = (self.image_depth, self.image_height, self.image_width)
+        size, step = PP.spacing_resample_size(arr.shape, tuple(reversed(newSpacing)), tuple(reversed(src_spacing)))
+
+        def probs_of(batch):
+            with torch.no_grad():
+                return self.model(batch)[1].detach().float()
+        with self._lock:
+            self.clear_GPU_cache()
+            self.model.eval()
+            vol = torch.as_tensor(np.ascontiguousarray(arr, dtype=np.float32)).to(self.device)
+            resized = PP.resample3d(vol, size, step, PP.LINEAR)
+            if clip is not None:
+                resized = PP.normalize_meanstd(resized, float(clip[0]), float(clip[1]))
+            elif self._norm3d == "meanstd":
+                resized = PP.normalize_meanstd(resized, -100.0, 100.0)
+            else:
+                resized = PP.normalize_percentile(resized)
+            out = PP.sliding_window_predict(probs_of, resized, patch, self.numclass, self.batch_size, overlap, blend, mirror_axes, 0.5,
+                                            self._mask_scale, return_probs)
+            mask, probs = out if return_probs else (out, None)
+            back_size, back_step = PP.spacing_resample_size(size, tuple(reversed(src_spacing)), tuple(reversed(newSpacing)))
+            back = PP.resample3d(mask, back_size, back_step, PP.NEAREST)
+            final = torch.zeros(arr.shape, dtype=torch.uint8, device=self.device)
+            m = [min(a, b) for a, b in zip(arr.shape, back_size)]
+            final[:m[0], :m[1], :m[2]] = back[:m[0], :m[1], :m[2]]
+            final = self._postprocessed(final).cpu().numpy().astype(arr.dtype)
+        result = self._like(image_sitk, final)
+        return (result, probs) if return_probs else result
 
     def clear_GPU_cache(self):
         if torch.cuda.is_available():

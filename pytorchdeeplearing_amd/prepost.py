@@ -1,7 +1,8 @@
 """Device-side pre/post-processing either side of `predict`: the SimpleITK resampling, the two
 intensity normalisations and the sliding-window crop / stitch of the reference's `inference` / `inference_patch`
 (model/modelVNet.py:678-698, model/modelUnet.py:684-763, dataprocess/utils.py:99-204), as HIP kernels behind the C-ABI
-(`seg_op_resample3d`, `seg_op_normalize_*`, `seg_op_gather_patches`, `seg_op_stitch_mask`).  Volumes are (D, H, W)
+(`seg_op_resample3d`, `seg_op_normalize_*`, `seg_op_gather_patches`, `seg_op_stitch_mask`), and sliding-window inference with
+blended class probabilities (`seg_op_gather_windows`, `seg_op_blend_windows`, `seg_op_blend_finalize`).  Volumes are (D, H, W)
 torch tensors on the engine's device; no CPU fallback (a CPU tensor raises unless the test-only checker is injected)."""
 import numpy as np
 import torch
@@ -118,6 +119,143 @@ def stitch_mask(masks, origins, out):
     lib.check(lib.seg_op_stitch_mask(masks.data_ptr(), origins.data_ptr(), nb, *pshape, out.data_ptr(), *out.shape,
                                      _capi.stream_for(out.device)), "seg_op_stitch_mask")
     return out
+
+
+# ---- sliding-window inference with blended probabilities (csrc/sliding.hip); no counterpart in the reference ----
+
+def _axis_starts(n, p, overlap):
+    if n <= p:
+        return [0]
+    step = max(1, int(p * (1.0 - overlap)))
+    starts = list(range(0, n - p + 1, step))
+    if starts[-1] != n - p:
+        starts.append(n - p)
+    return starts
+
+
+def window_origins(vol_shape, patch_shape, overlap=0.5):
+    """Origins (z, y, x) of overlapping windows that cover the volume, z-major with x fastest.  Per axis: the single start 0 when the
+    volume is not larger than the patch (the window then overhangs and `gather_windows` pads it); otherwise 0, step, 2 * step, ... while
+    the window fits, step = max(1, int(patch * (1 - overlap))), plus the start that ends on the far border when the last one does not."""
+    if not 0.0 <= overlap < 1.0:
+        raise ValueError("overlap must lie in [0, 1), got %r" % (overlap,))
+    if len(vol_shape) != 3 or len(patch_shape) != 3:
+        raise ValueError("window_origins expects (D, H, W) shapes")
+    zs, ys, xs = (_axis_starts(int(n), int(p), float(overlap)) for n, p in zip(vol_shape, patch_shape))
+    return [(z, y, x) for z in zs for y in ys for x in xs]
+
+
+def importance_1d(p, mode="gaussian"):
+    """fp32 importance weights along one patch axis: "constant" = ones; "gaussian" = exp(-(i - (p - 1) / 2)^2 / (2 * (0.125 * p)^2)) divided
+    by its maximum and floored at 1e-3 (so the weight sum of a covered voxel is never 0).  The blend weight of a window voxel is the product
+    of the three axes' values."""
+    p = int(p)
+    if mode == "constant":
+        return np.ones(p, np.float32)
+    if mode != "gaussian":
+        raise ValueError("blend must be 'constant' or 'gaussian', got %r" % (mode,))
+    i = np.arange(p, dtype=np.float64)
+    g = np.exp(-(i - (p - 1) / 2.0) ** 2 / (2.0 * (0.125 * p) ** 2))
+    return np.maximum(g / g.max(), 1e-3).astype(np.float32)
+
+
+def _entries(entries, device):
+    """window entries {z, y, x, flipbits} as a contiguous int32 (nb, 4) tensor on `device`"""
+    e = torch.as_tensor(entries, dtype=torch.int32).to(device).contiguous()
+    if e.dim() != 2 or e.shape[1] != 4 or e.shape[0] < 1:
+        raise RuntimeError("window entries must be a non-empty (nb, 4) list of {z, y, x, flipbits}")
+    return e
+
+
+def gather_windows(vol, entries, patch_shape, pad_value=0.0):
+    """(D, H, W) float32 volume + int32 entries (nb, 4) {z, y, x, flipbits} on the device -> (nb, 1, pd, ph, pw) network batch; bit 0 / 1 / 2
+    of flipbits mirrors the window along z / y / x, voxels outside the volume read `pad_value`."""
+    vol = _vol(vol.float())
+    e = _entries(entries, vol.device)
+    lib = _capi.lib_for(vol.device)
+    patch_shape = tuple(int(s) for s in patch_shape)
+    out = torch.empty((e.shape[0], 1) + patch_shape, dtype=torch.float32, device=vol.device)
+    lib.check(lib.seg_op_gather_windows(vol.data_ptr(), *vol.shape, e.data_ptr(), e.shape[0], *patch_shape, float(pad_value), out.data_ptr(),
+                                        _capi.stream_for(vol.device)), "seg_op_gather_windows")
+    return out
+
+
+def _f32c(t, device):
+    return torch.as_tensor(t, dtype=torch.float32).to(device).contiguous()
+
+
+def blend_windows(probs, entries, weights, acc, wsum, box=None):
+    """acc (C, D, H, W) += w * probs, wsum (D, H, W) += w for the windows of one batch, un-mirrored back into the volume, w = wz[i] * wy[j] * wx[k]
+    (`weights` = the three 1-D importance vectors).  probs: (nb, C, pd, ph, pw) fp32.  `box` = ((z0, y0, x0), (z1, y1, x1)), half-open, the voxels
+    the launch covers: it must hold every window of the batch (default: the whole volume; `sliding_window_predict` passes the windows' bounding box).
+    Deterministic: windows are added in entry order."""
+    if probs.dim() != 5 or acc.dim() != 4 or wsum.dim() != 3 or tuple(acc.shape[1:]) != tuple(wsum.shape) or probs.shape[1] != acc.shape[0]:
+        raise RuntimeError("blend_windows: expected probs (nb, C, pd, ph, pw), acc (C, D, H, W) and wsum (D, H, W), got %s, %s, %s"
+                           % (tuple(probs.shape), tuple(acc.shape), tuple(wsum.shape)))
+    if acc.dtype != torch.float32 or wsum.dtype != torch.float32 or not acc.is_contiguous() or not wsum.is_contiguous():
+        raise RuntimeError("blend_windows: acc and wsum must be contiguous float32 tensors")
+    dev = acc.device
+    probs = _f32c(probs, dev)
+    e = _entries(entries, dev)
+    nb, c, pd, ph, pw = probs.shape
+    w3 = [_f32c(w, dev) for w in weights]
+    if e.shape[0] != nb or [w.numel() for w in w3] != [pd, ph, pw]:
+        raise RuntimeError("blend_windows: %d entries and importance vectors of %s elements for probs %s"
+                           % (e.shape[0], [w.numel() for w in w3], tuple(probs.shape)))
+    lo, hi = box if box is not None else ((0, 0, 0), tuple(wsum.shape))
+    I3 = _capi.C.c_int * 3
+    lib = _capi.lib_for(dev)
+    lib.check(lib.seg_op_blend_windows(probs.data_ptr(), e.data_ptr(), nb, c, pd, ph, pw, w3[0].data_ptr(), w3[1].data_ptr(), w3[2].data_ptr(),
+                                       I3(*(int(v) for v in lo)), I3(*(int(v) for v in hi)), acc.data_ptr(), wsum.data_ptr(), *wsum.shape,
+                                       _capi.stream_for(dev)), "seg_op_blend_windows")
+    return acc, wsum
+
+
+def blend_finalize(acc, wsum, threshold=0.5, scale=1, return_probs=False):
+    """blended field -> uint8 mask (D, H, W): C == 1: (acc / wsum > threshold) * scale, C > 1: first arg-max over the classes; with
+    return_probs also acc / wsum as (C, D, H, W) fp32.  A voxel no window reached (wsum == 0) gives mask 0 and probability 0."""
+    if acc.dim() != 4 or tuple(acc.shape[1:]) != tuple(wsum.shape) or acc.dtype != torch.float32 or wsum.dtype != torch.float32:
+        raise RuntimeError("blend_finalize: expected float32 acc (C, D, H, W) and wsum (D, H, W), got %s, %s" % (tuple(acc.shape), tuple(wsum.shape)))
+    acc, wsum = acc.contiguous(), wsum.contiguous()
+    lib = _capi.lib_for(acc.device)
+    mask = torch.empty(wsum.shape, dtype=torch.uint8, device=acc.device)
+    probs = torch.empty_like(acc) if return_probs else None
+    lib.check(lib.seg_op_blend_finalize(acc.data_ptr(), wsum.data_ptr(), acc.shape[0], wsum.numel(), float(threshold), int(scale), mask.data_ptr(),
+                                        probs.data_ptr() if return_probs else None, _capi.stream_for(acc.device)), "seg_op_blend_finalize")
+    return (mask, probs) if return_probs else mask
+
+
+def sliding_window_predict(fn, vol, patch, num_class, batch_size=1, overlap=0.5, blend="gaussian", mirror_axes=(), threshold=0.5, scale=1,
+                           return_probs=False):
+    """Whole-volume prediction from a patch network.  vol: device fp32 (D, H, W); fn: device batch (B, 1, pd, ph, pw) -> class probabilities
+    (B, C, pd, ph, pw) fp32.  The entry list is every `window_origins` origin x every subset of `mirror_axes` (0 = z, 1 = y, 2 = x); it runs in
+    batches of `batch_size` through gather_windows -> fn -> blend_windows (fn always sees `batch_size` windows when there are more entries than
+    that), then blend_finalize: the uint8 mask (D, H, W), with return_probs also the blended probabilities (C, D, H, W).  A 2-D image is
+    D = pd = 1."""
+    vol = _vol(vol.float())
+    patch = tuple(int(s) for s in patch)
+    axes = sorted(set(int(a) for a in mirror_axes))
+    if any(a not in (0, 1, 2) for a in axes):
+        raise ValueError("mirror_axes must be a subset of (0, 1, 2)")
+    flips = [sum(1 << a for k, a in enumerate(axes) if s >> k & 1) for s in range(1 << len(axes))]
+    entries = [o + (f,) for o in window_origins(vol.shape, patch, overlap) for f in flips]
+    weights = [torch.from_numpy(importance_1d(p, blend)).to(vol.device) for p in patch]
+    acc = torch.zeros((int(num_class),) + tuple(vol.shape), dtype=torch.float32, device=vol.device)
+    wsum = torch.zeros(tuple(vol.shape), dtype=torch.float32, device=vol.device)
+    bs = max(1, int(batch_size))
+    for s in range(0, len(entries), bs):
+        chunk = entries[s:s + bs]
+        # a short last batch is filled up with repeats of its last window, so that fn sees ONE batch size (an engine behind fn plans per batch
+        # shape); only the first len(chunk) answers are blended
+        fed = chunk + [chunk[-1]] * (bs - len(chunk) if len(entries) > bs else 0)
+        e = torch.tensor(fed, dtype=torch.int32).to(vol.device)
+        probs = fn(gather_windows(vol, e, patch))
+        if tuple(probs.shape) != (len(fed), int(num_class)) + patch:
+            raise RuntimeError("sliding_window_predict: fn returned %s for a batch of %s" % (tuple(probs.shape), (len(fed), int(num_class)) + patch))
+        lo = tuple(min(c[a] for c in chunk) for a in range(3))
+        hi = tuple(min(max(c[a] for c in chunk) + patch[a], vol.shape[a]) for a in range(3))
+        blend_windows(probs[:len(chunk)], e[:len(chunk)], weights, acc, wsum, (lo, hi))
+    return blend_finalize(acc, wsum, threshold, scale, return_probs)
 
 
 # ---- mask post-processing (dataprocess/utils.py:7-96): connected components and binary morphology, csrc/postproc.hip ----
