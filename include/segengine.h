@@ -433,7 +433,8 @@ typedef struct seg_pack_desc {
                    lane = 16*((c%32)/8) + row%16 holds k = c%8 .. — one 16x32 B fragment is one contiguous 1 KB line;
                    2: the same over the flat k = t*Cc + c axis, [Kpad/32][rows/16][64 lanes][8] (Cc == 16: two taps per step);
                    3: Cc == 16, T == 27, Kpad == 480: [15 steps = kh*5 + pair][rows/16][64 lanes][8], the two taps of a step differ in kd / kw only -
-                      pairs 0..2: (kd = pair, kw = 0 | 1), 3: (kd = 0 | 1, kw = 2), 4: (kd = 2, kw = 2 | zeros) (seg_op_conv3x_cfg_frag) */
+                      pairs 0..2: (kd = pair, kw = 0 | 1), 3: (kd = 0 | 1, kw = 2), 4: (kd = 2, kw = 2 | zeros); read by the tilings whose
+                      seg_op_conv3x_cfg_frag(cfg) is 3 */
 } seg_pack_desc;
 int seg_op_pack(const seg_pack_desc* descs, int ndesc, long long max_elems, int dtype, void* stream);
 /* LDS halo-tile kernels for the 3^d (ndim 3) / 3^2 (ndim 2, D = 1) stride-1 pad-1 convolutions.
@@ -490,8 +491,8 @@ int seg_op_conv3x_num_cfgs(void);
 /* index in [0, num_cfgs): tiling id, ndim, box {d,h,w}, output channels per workgroup, resident 32-channel chunks, description */
 int seg_op_conv3x_cfg_info(int index, int* id, int* ndim, int* box3, int* bn, int* nres, char* name, int name_cap);
 int seg_op_conv3x_default_cfg(int ndim, int n, int d, int h, int wid, int cin, int cout, int dtype);
-/* seg_pack_desc.frag of the weights tiling `cfg` reads: 1, 2 (Cin == 16) or 3 (Cin == 16, 3-D tilings 28 .. 29: the halo fragments are reused across
- * the kh taps, csrc/conv3x_impl.h conv3x16r_kernel); 0 for an unknown id */
+/* seg_pack_desc.frag of the weights tiling `cfg` reads: 1, 2 (Cin == 16) or 3 (Cin == 16, 3-D, the halo fragments reused across the kh taps:
+ * csrc/conv3x_impl.h conv3x16r_kernel); 0 for an unknown id.  This call, not an id range, says which layout a tiling reads (today 3 for tilings 28 and 29) */
 int seg_op_conv3x_cfg_frag(int cfg);
 /* sizeof of the structs of this header as compiled into the library: 0 conv, 1 wgrad, 2 pack, 3 stemx, 4 train, 5 gn_fwd, 6 gn_bwd */
 int seg_abi_sizeof(int which);

@@ -1,77 +1,36 @@
-// Host side of the register-blocked halo conv (kernel: conv3x_impl.h; instantiations: conv3x_<dtype>_<nd>.hip): the table of
-// tilings, the default choice per layer shape and the launch entry points declared in kernels.h.
+// Host side of the register-blocked halo conv (kernels and the table of tilings: conv3x_impl.h; instantiations: conv3x_<dtype>_<nd>.hip): what a tiling
+// covers, the default choice per layer shape and the launch entry points declared in kernels.h.
 #include <vector>
 #include "conv3x_impl.h"
 
 namespace seg {
 namespace {
-using c3x::Conv3xArgs;
+using namespace c3x;
 
-struct Cfg { int id, ndim, td, th, tw, bn, nres; const char* name; int cin16 = 0; };   // cin16: the Cin == 16 kernel (two taps per MFMA step)
-
-// id, ndim, box, BN, resident chunks — kept in sync with SEG_C3X_3D_BODY / SEG_C3X_2D_BODY (conv3x_impl.h)
-const Cfg kCfgs[] = {
-    // 3-D
-    {0, 3, 2, 8, 16, 32, 1, "2x8x16 t16 4x1 waves 4x2 tiles"},
-    {1, 3, 4, 8, 16, 32, 1, "4x8x16 t16 4x1 waves 8x2 tiles"},
-    {2, 3, 2, 8, 16, 64, 2, "2x8x16 t16 2x2 waves 8x2 tiles"},
-    {3, 3, 2, 8, 8, 64, 2, "2x8x8 t8 2x2 waves 4x2 tiles"},
-    {4, 3, 4, 8, 8, 64, 2, "4x8x8 t8 2x2 waves 8x2 tiles"},
-    {5, 3, 4, 8, 8, 64, 2, "4x8x8 t8 4x1 waves 4x4 tiles"},
-    {6, 3, 2, 8, 8, 64, 2, "2x8x8 t8 4x1 waves 2x4 tiles"},
-    {7, 3, 2, 4, 12, 64, 4, "2x4x12 t4 2x2 waves 3x2 tiles"},
-    {8, 3, 4, 4, 12, 64, 4, "4x4x12 t4 2x2 waves 6x2 tiles"},
-    {9, 3, 2, 4, 12, 128, 4, "2x4x12 t4 2x2 waves 3x4 tiles"},
-    {10, 3, 2, 8, 16, 16, 1, "2x8x16 t16 4x1 waves 4x1 tiles"},
-    {11, 3, 2, 8, 8, 64, 4, "2x8x8 t8 2x2 waves 4x2 tiles, 4 resident chunks"},
-    {12, 3, 2, 8, 8, 128, 4, "2x8x8 t8 2x2 waves 4x4 tiles, 4 resident chunks"},
-    {13, 3, 2, 8, 8, 32, 2, "2x8x8 t8 4x1 waves 2x2 tiles"},
-    {14, 3, 4, 8, 8, 32, 1, "4x8x8 t8 4x1 waves 4x2 tiles"},
-    {15, 3, 2, 8, 16, 32, 2, "2x8x16 t16 4x1 waves 4x2 tiles, 2 resident chunks"},
-    {16, 3, 2, 8, 16, 32, 1, "2x8x16 t16 4x1 waves 4x2 tiles, deep B ring, 2 workgroups/CU"},
-    {17, 3, 4, 8, 8, 32, 1, "4x8x8 t8 4x1 waves 4x2 tiles, deep B ring, 2 workgroups/CU"},
-    {20, 3, 4, 8, 8, 32, 1, "4x8x8 t8 4x1 waves 4x2 tiles, 3 workgroups/CU"},
-    {21, 3, 2, 8, 8, 32, 1, "2x8x8 t8 4x1 waves 2x2 tiles, 1 resident chunk, 4 workgroups/CU"},
-    {22, 3, 2, 8, 8, 32, 1, "2x8x8 t8 4x1 waves 2x2 tiles, 1 resident chunk, deep B ring, 3 workgroups/CU"},
-    {23, 3, 4, 8, 8, 32, 1, "4x8x8 t8 4x1 waves 4x2 tiles, deep B ring, 3 workgroups/CU"},
-    // the deep 12^3 / 6^3 levels are weight-stream latency chains (one L2 round trip per 8 steps of 6 MFMAs): a whole chunk of taps in flight
-    // (PF = 26), and 32 output channels per workgroup = twice the workgroups, each streaming half the weights
-    {44, 3, 2, 4, 12, 64, 4, "2x4x12 t4 2x2 waves 3x2 tiles, 26-deep B ring"},
-    {45, 3, 2, 4, 12, 32, 4, "2x4x12 t4 2x2 waves 3x1 tiles, 26-deep B ring"},
-    {46, 3, 2, 4, 12, 32, 4, "2x4x12 t4 2x2 waves 3x1 tiles"},
-    {47, 3, 4, 4, 12, 32, 4, "4x4x12 t4 2x2 waves 6x1 tiles"},
-    {48, 3, 4, 4, 12, 32, 4, "4x4x12 t4 2x2 waves 6x1 tiles, 26-deep B ring"},
-    {49, 3, 2, 4, 12, 64, 4, "2x4x12 t4 1x4 waves 6x1 tiles (every wave its own weight columns)"},
-    {50, 3, 2, 4, 12, 64, 4, "2x4x12 t4 1x4 waves 6x1 tiles, 26-deep B ring"},
-    {24, 3, 2, 8, 16, 16, 1, "Cin16: 2x8x16 t16 4x1 waves 4x1 tiles", 1},
-    {25, 3, 4, 8, 16, 16, 1, "Cin16: 4x8x16 t16 4x1 waves 8x1 tiles", 1},
-    {26, 3, 2, 8, 16, 32, 1, "Cin16: 2x8x16 t16 4x1 waves 4x2 tiles", 1},
-    {27, 3, 4, 8, 16, 32, 1, "Cin16: 4x8x16 t16 4x1 waves 8x2 tiles", 1},
-    // Cin == 16, halo fragments reused across the kh taps (conv3x16r_kernel; weights packed with frag = 3: cin16 = 2)
-    {28, 3, 2, 8, 16, 16, 1, "Cin16 row reuse: 2x8x16 t16 4x1 waves 4x1 tiles", 2},
-    {29, 3, 4, 8, 16, 16, 1, "Cin16 row reuse: 4x8x16 t16 4x1 waves 8x1 tiles", 2},
-    // 2-D
-    {32, 2, 1, 16, 16, 32, 1, "16x16 t16 4x1 waves 4x2 tiles"},
-    {33, 2, 1, 16, 16, 64, 2, "16x16 t16 2x2 waves 8x2 tiles"},
-    {34, 2, 1, 8, 16, 64, 2, "8x16 t16 2x2 waves 4x2 tiles"},
-    {35, 2, 1, 8, 16, 64, 4, "8x16 t16 2x2 waves 4x2 tiles, 4 resident chunks"},
-    {36, 2, 1, 8, 16, 128, 4, "8x16 t16 2x2 waves 4x4 tiles, 4 resident chunks"},
-    {37, 2, 1, 16, 16, 16, 1, "16x16 t16 4x1 waves 4x1 tiles"},
-    {38, 2, 1, 8, 8, 64, 4, "8x8 t8 2x2 waves 2x2 tiles, 4 resident chunks"},
-    {39, 2, 1, 8, 16, 32, 2, "8x16 t16 4x1 waves 2x2 tiles, 2 resident chunks"},
-    {56, 2, 1, 16, 16, 16, 1, "Cin16: 16x16 t16 4x1 waves 4x1 tiles", 1},
-    {57, 2, 1, 16, 16, 32, 1, "Cin16: 16x16 t16 4x1 waves 4x2 tiles", 1},
-};
-constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
-
-const Cfg* find_cfg(int id) {
-    for (int i = 0; i < kNumCfgs; ++i)
-        if (kCfgs[i].id == id) return &kCfgs[i];
+const Tiling* find_cfg(int id) {
+    for (int i = 0; i < kNumTilings; ++i)
+        if (kTilings[i].id == id) return &kTilings[i];
     return nullptr;
 }
 
-bool cfg_fits(const Cfg& c, int ndim, int Cin, int Cout) {
-    return c.ndim == ndim && Cout % c.bn == 0 && (c.cin16 != 0) == (Cin == 16);
+bool cfg_fits(const Tiling& c, int ndim, int Cin, int Cout) {
+    return c.ndim == ndim && Cout % c.bn() == 0 && (c.kind != K_CONV) == (Cin == 16);
+}
+
+// "<kind: >box t<tile width> <wave grid> waves <register tiles> tiles, <n> resident, ring <pf>, <occ> wg/CU" (tools/tune_conv3x.py prints it)
+const char* cfg_name(int index) {
+    static char names[kNumTilings][96];
+    static const bool once = [] {
+        for (int i = 0; i < kNumTilings; ++i) {
+            const Tiling& t = kTilings[i];
+            int n = snprintf(names[i], 96, "%s", t.kind == K_C16R ? "Cin16 row reuse: " : (t.kind == K_C16 ? "Cin16: " : ""));
+            if (t.ndim == 3) n += snprintf(names[i] + n, 96 - n, "%dx", t.td);
+            snprintf(names[i] + n, 96 - n, "%dx%d t%d %dx%d waves %dx%d tiles, %d resident, ring %d, %d wg/CU", t.th, t.tw, t.tx, t.wm, t.wn, t.tm, t.tn, t.nres, t.pf, t.occ);
+        }
+        return true;
+    }();
+    (void)once;
+    return names[index];
 }
 
 }  // namespace
@@ -95,7 +54,7 @@ int conv3x_pick(int ndim, int N, int D, int H, int W, int Cin, int Cout, bool ha
         for (const char* p = map; *p;) {
             int ci = 0, co = 0, w = 0, id = -1;
             if (sscanf(p, "%d:%d:%d=%d", &ci, &co, &w, &id) == 4 && ci == Cin && co == Cout && w == W) {
-                const Cfg* c = find_cfg(id);
+                const Tiling* c = find_cfg(id);
                 if (c && cfg_fits(*c, ndim, Cin, Cout)) return id;
             }
             while (*p && *p != ',') ++p;
@@ -109,7 +68,7 @@ int conv3x_pick(int ndim, int N, int D, int H, int W, int Cin, int Cout, bool ha
     const long long vox = (long long)N * D * H * W;
     int id;
     if (Cin == 16) {
-        // 3-D: the row-reuse kernel (28 .. 31 = 24 .. 27 with a third of the LDS fragment reads); SEG_C3X16_REUSE=0: the one-read-per-MFMA kernel
+        // 3-D: the row-reuse kernel (28 / 29 = 24 / 25 with a third of the LDS fragment reads); SEG_C3X16_REUSE=0: the one-read-per-MFMA kernel
         static const int reuse = knob_i("SEG_C3X16_REUSE", 1);
         // (measured and not kept, profiles/r06_conv3x16_row_reuse_*: the row-reuse form with two output tiles per wave = 32 output channels, 175 / 162 vs
         // 165 / 157 us at 2 x 128^3; four / five workgroups per CU instead of three / four: equal inside the step)
@@ -134,8 +93,8 @@ int conv3x_pick(int ndim, int N, int D, int H, int W, int Cin, int Cout, bool ha
             // flight: 19.2 -> 14.4 us at 4 x 6^3 x 256, 19.0 -> 14.3 at 1 x 10^3, 19.4 -> 14.4 at 2 x 8^3, 11.7 -> 9.5 at 2 x 16^3 x 128 -> 64
             // (profiles/r04_deep_level_tilings.log); +1.0 ... +1.4 % on the train step on two leases.  Only while the doubled grid still fits the
             // 256 CUs in one round (12^3 x 128 x 4 samples: 144 -> 288 workgroups, 11.5 -> 16.3 us).
-            const long long nb = (long long)N * ((D + 1) / 2) * ((H + 3) / 4) * ((W + 11) / 12);
-            if (Cout % 64 == 0 && nb * (Cout / 64) <= 128) id = 45;
+            const Tiling* deep = find_cfg(45);
+            if (deep && Cout % 64 == 0 && num_boxes(deep->td, deep->th, deep->tw, N, D, H, W) * (Cout / 64) <= 128) id = deep->id;
         }
         else id = Cin >= 128 ? 5 : 3;
     } else {
@@ -143,34 +102,34 @@ int conv3x_pick(int ndim, int N, int D, int H, int W, int Cin, int Cout, bool ha
         else if (Cout % 64) id = 32;
         else id = Cin >= 256 ? 35 : 33;
     }
-    const Cfg* c = find_cfg(id);
+    const Tiling* c = find_cfg(id);
     if (c && cfg_fits(*c, ndim, Cin, Cout)) return id;
-    for (int i = 0; i < kNumCfgs; ++i)
-        if (cfg_fits(kCfgs[i], ndim, Cin, Cout)) return kCfgs[i].id;
+    for (int i = 0; i < kNumTilings; ++i)
+        if (cfg_fits(kTilings[i], ndim, Cin, Cout)) return kTilings[i].id;
     return -1;
 }
 
 // weight layout a tiling reads (seg_pack_desc.frag): 1 fragment-major per (chunk, tap), 2 flat k axis (Cin == 16), 3 taps paired within a kh row (conv3x16r_kernel)
 int conv3x_cfg_frag(int cfg) {
-    const Cfg* c = find_cfg(cfg);
-    return !c ? 0 : (c->cin16 == 2 ? 3 : (c->cin16 ? 2 : 1));
+    const Tiling* c = find_cfg(cfg);
+    return c ? c->frag() : 0;
 }
-int conv3x_num_cfgs() { return kNumCfgs; }
+int conv3x_num_cfgs() { return kNumTilings; }
 int conv3x_cfg_info(int index, int* id, int* ndim, int* box3, int* bn, int* nres, const char** name) {
-    if (index < 0 || index >= kNumCfgs) return -1;
-    const Cfg& c = kCfgs[index];
+    if (index < 0 || index >= kNumTilings) return -1;
+    const Tiling& c = kTilings[index];
     if (id) *id = c.id;
     if (ndim) *ndim = c.ndim;
     if (box3) { box3[0] = c.td; box3[1] = c.th; box3[2] = c.tw; }
-    if (bn) *bn = c.bn;
+    if (bn) *bn = c.bn();
     if (nres) *nres = c.nres;
-    if (name) *name = c.name;
+    if (name) *name = cfg_name(index);
     return 0;
 }
 
 bool launch_conv3x(int cfg, const void* in0, const void* in1, int C0, const void* w, const float* bias, void* out, double* stats, int N, int D,
                    int H, int W, int Cin, int Cout, int ndim, int dtype, hipStream_t s, int stat_rep) {
-    const Cfg* c = find_cfg(cfg);
+    const Tiling* c = find_cfg(cfg);
     if (!c || !cfg_fits(*c, ndim, Cin, Cout) || !conv3x_supported(dtype, ndim, N, D, H, W, Cin, Cout, C0, in1 != nullptr)) return false;
     Conv3xArgs a;
     a.in0 = in0; a.in1 = in1; a.C0 = in1 ? C0 : Cin; a.w = w; a.bias = bias; a.out = out; a.stats = stats;

@@ -4,8 +4,7 @@
 namespace seg {
 namespace c3x {
 template <> bool launch_2d<bf16>(int id, const Conv3xArgs& a, hipStream_t s) {
-    typedef bf16 T;
-    SEG_C3X_2D_BODY
+    return launch_nd<bf16, 2>(id, a, s, Rows{});
 }
 }  // namespace c3x
 }  // namespace seg

@@ -17,13 +17,12 @@
 #pragma once
 #include <cstdio>
 #include <cstdlib>
+#include <utility>
 
 #include "kernels.h"
 
 namespace seg {
 namespace c3x {
-
-__device__ __forceinline__ int halo_swz_x(int row, int x) { return ((row & 1) << 1) ^ (((x >> 2) & 1) * 3); }   // = conv3.hip halo_swz
 
 // Box of TD x TH x TW output voxels cut into 16-voxel M tiles of TY x TX (1x16, 2x8 or 4x4) voxels; voxel order is tile-major.
 template <int TD_, int TH_, int TW_, int KD_, int TX_> struct XBox {
@@ -200,7 +199,7 @@ __global__ __launch_bounds__(256, OCC) void conv3x_kernel(Conv3xArgs a) {
         const int z = z0 + hz - B::PD, y = y0 + hy - 1, x = x0 + hx - 1;
         const bool ok = i < B::NINSTR && row < B::ROWS && hx < B::HW && (unsigned)z < (unsigned)a.D && (unsigned)y < (unsigned)a.H &&
                         (unsigned)x < (unsigned)a.W;
-        src[u] = ok ? ((((z * a.H) + y) * a.W + x) << 2) + (slot ^ halo_swz_x(row, hx)) : -1;
+        src[u] = ok ? ((((z * a.H) + y) * a.W + x) << 2) + (slot ^ halo_swz(row, hx)) : -1;
     }
     const long long vol = (long long)a.D * a.H * a.W;
     const int C1 = a.Cin - a.C0;
@@ -252,7 +251,7 @@ __global__ __launch_bounds__(256, OCC) void conv3x_kernel(Conv3xArgs a) {
         B::vox((wm * TM + m) * 16 + l15, vz, vy, vx);
         const int row = vz * B::HH + vy;
 #pragma unroll
-        for (int kw = 0; kw < 3; ++kw) ab[m][kw] = (row * B::HWP + vx) * 32 + ((q ^ halo_swz_x(row, vx + kw)) << 3);
+        for (int kw = 0; kw < 3; ++kw) ab[m][kw] = (row * B::HWP + vx) * 32 + ((q ^ halo_swz(row, vx + kw)) << 3);
     }
 
     f32x4 acc[TM][TN];
@@ -326,14 +325,6 @@ __global__ __launch_bounds__(256, OCC) void conv3x_kernel(Conv3xArgs a) {
     SEG_C3XT(3);
 }
 
-
-template <class T, class B, int TM, int TN, int WM, int WN, int NRES, int PF, int OCC>
-void launch_cfg(const Conv3xArgs& a, hipStream_t s) {
-    constexpr int BN = WN * TN * 16;
-    const long long nbox = (long long)a.N * ((a.D + B::TD - 1) / B::TD) * ((a.H + B::TH - 1) / B::TH) * ((a.W + B::TW - 1) / B::TW);
-    dim3 grid(a.remap ? (unsigned)((nbox + 7) / 8 * 8) : (unsigned)nbox, a.Cout / BN);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x_kernel<T, B, TM, TN, WM, WN, NRES, PF, OCC>), grid, dim3(256), 0, s, a);
-}
 
 
 
@@ -550,79 +541,136 @@ __global__ __launch_bounds__(256, OCC) void conv3x16r_kernel(Conv3xArgs a) {
     c3x_epilogue<T, B, TM, TN, WM, 1>(acc, red_s, a, n, x0, y0, z0, co0, bias_s);
 }
 
-template <class T, class B, int TM, int TN, int OCC>
-void launch_cfg16r(const Conv3xArgs& a, hipStream_t s) {
-    const long long nbox = (long long)a.N * ((a.D + B::TD - 1) / B::TD) * ((a.H + B::TH - 1) / B::TH) * ((a.W + B::TW - 1) / B::TW);
-    dim3 grid(a.remap ? (unsigned)((nbox + 7) / 8 * 8) : (unsigned)nbox, a.Cout / (TN * 16));
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x16r_kernel<T, B, TM, TN, OCC>), grid, dim3(256), 0, s, a);
+// ------------------------------------------------------------------------------------------------
+// The tilings.  This table is the ONLY place a tiling is written down: the kernels are instantiated from its rows (launch_nd below) and the host
+// side (conv3x.hip: the Cout a tiling covers, the weight layout it reads, seg_op_conv3x_cfg_info, the default pick) reads the same rows.  The row
+// order is the enumeration order of seg_op_conv3x_cfg_info.  Adding a tiling is adding a row ("conv3x tilings").
+// ------------------------------------------------------------------------------------------------
+enum Kind { K_CONV, K_C16, K_C16R };          // conv3x_kernel | conv3x16_kernel | conv3x16r_kernel
+struct Tiling {
+    int id, ndim, kind;
+    int td, th, tw, tx;                       // box of output voxels; width of its 16-voxel M tiles
+    int tm, tn, wm, wn;                       // register tiles per wave; wave grid (the Cin == 16 kernels fix 4 x 1)
+    int nres, pf, occ;                        // resident 32-channel chunks (Cin == 16: 1); weight steps in flight ahead of the MFMAs (conv3x16r_kernel holds all 15: 14); workgroups / CU
+    constexpr int kd() const { return ndim == 3 ? 3 : 1; }
+    constexpr int bn() const { return wn * tn * 16; }          // output channels per workgroup
+    constexpr int frag() const { return kind == K_C16R ? 3 : (kind == K_C16 ? 2 : 1); }     // seg_pack_desc.frag of the weights it reads
+};
+constexpr Tiling kTilings[] = {
+    // id nd kind      td  th  tw  tx  tm tn wm wn nres pf occ
+    {0,  3, K_CONV,    2,  8, 16, 16,  4, 2, 4, 1, 1,  2, 2},
+    {1,  3, K_CONV,    4,  8, 16, 16,  8, 2, 4, 1, 1,  2, 1},
+    {2,  3, K_CONV,    2,  8, 16, 16,  8, 2, 2, 2, 2,  8, 1},
+    {3,  3, K_CONV,    2,  8,  8,  8,  4, 2, 2, 2, 2,  8, 2},
+    {4,  3, K_CONV,    4,  8,  8,  8,  8, 2, 2, 2, 2,  8, 1},
+    {5,  3, K_CONV,    4,  8,  8,  8,  4, 4, 4, 1, 2,  2, 1},
+    {6,  3, K_CONV,    2,  8,  8,  8,  2, 4, 4, 1, 2,  2, 2},
+    {7,  3, K_CONV,    2,  4, 12,  4,  3, 2, 2, 2, 4,  8, 1},
+    {8,  3, K_CONV,    4,  4, 12,  4,  6, 2, 2, 2, 4,  8, 1},
+    {9,  3, K_CONV,    2,  4, 12,  4,  3, 4, 2, 2, 4,  2, 1},
+    {10, 3, K_CONV,    2,  8, 16, 16,  4, 1, 4, 1, 1,  8, 2},
+    {11, 3, K_CONV,    2,  8,  8,  8,  4, 2, 2, 2, 4,  8, 1},
+    {12, 3, K_CONV,    2,  8,  8,  8,  4, 4, 2, 2, 4,  2, 1},
+    {13, 3, K_CONV,    2,  8,  8,  8,  2, 2, 4, 1, 2,  8, 2},
+    {14, 3, K_CONV,    4,  8,  8,  8,  4, 2, 4, 1, 1,  2, 2},
+    {15, 3, K_CONV,    2,  8, 16, 16,  4, 2, 4, 1, 2,  8, 1},
+    {16, 3, K_CONV,    2,  8, 16, 16,  4, 2, 4, 1, 1,  8, 2},
+    {17, 3, K_CONV,    4,  8,  8,  8,  4, 2, 4, 1, 1,  8, 2},
+    {20, 3, K_CONV,    4,  8,  8,  8,  4, 2, 4, 1, 1,  2, 3},
+    {21, 3, K_CONV,    2,  8,  8,  8,  2, 2, 4, 1, 1,  2, 4},
+    {22, 3, K_CONV,    2,  8,  8,  8,  2, 2, 4, 1, 1,  8, 3},
+    {23, 3, K_CONV,    4,  8,  8,  8,  4, 2, 4, 1, 1,  8, 3},
+    // the deep 12^3 / 6^3 levels are weight-stream latency chains (one L2 round trip per 8 steps of 6 MFMAs): a whole chunk of taps in flight
+    // (pf = 26), and 32 output channels per workgroup = twice the workgroups, each streaming half the weights; 49 / 50: every wave its own weight columns
+    {44, 3, K_CONV,    2,  4, 12,  4,  3, 2, 2, 2, 4, 26, 1},
+    {45, 3, K_CONV,    2,  4, 12,  4,  3, 1, 2, 2, 4, 26, 1},
+    {46, 3, K_CONV,    2,  4, 12,  4,  3, 1, 2, 2, 4,  8, 1},
+    {47, 3, K_CONV,    4,  4, 12,  4,  6, 1, 2, 2, 4,  8, 1},
+    {48, 3, K_CONV,    4,  4, 12,  4,  6, 1, 2, 2, 4, 26, 1},
+    {49, 3, K_CONV,    2,  4, 12,  4,  6, 1, 1, 4, 4,  8, 1},
+    {50, 3, K_CONV,    2,  4, 12,  4,  6, 1, 1, 4, 4, 26, 1},
+    // Cin == 16: two taps per MFMA step
+    {24, 3, K_C16,     2,  8, 16, 16,  4, 1, 4, 1, 1,  2, 4},
+    {25, 3, K_C16,     4,  8, 16, 16,  8, 1, 4, 1, 1,  2, 3},
+    {26, 3, K_C16,     2,  8, 16, 16,  4, 2, 4, 1, 1,  2, 3},
+    {27, 3, K_C16,     4,  8, 16, 16,  8, 2, 4, 1, 1,  2, 2},
+    // Cin == 16, halo fragments reused across the kh taps
+    {28, 3, K_C16R,    2,  8, 16, 16,  4, 1, 4, 1, 1, 14, 4},
+    {29, 3, K_C16R,    4,  8, 16, 16,  8, 1, 4, 1, 1, 14, 3},
+    // 2-D
+    {32, 2, K_CONV,    1, 16, 16, 16,  4, 2, 4, 1, 1,  8, 2},
+    {33, 2, K_CONV,    1, 16, 16, 16,  8, 2, 2, 2, 2,  2, 2},
+    {34, 2, K_CONV,    1,  8, 16, 16,  4, 2, 2, 2, 2,  8, 2},
+    {35, 2, K_CONV,    1,  8, 16, 16,  4, 2, 2, 2, 4,  8, 2},
+    {36, 2, K_CONV,    1,  8, 16, 16,  4, 4, 2, 2, 4,  2, 2},
+    {37, 2, K_CONV,    1, 16, 16, 16,  4, 1, 4, 1, 1,  8, 3},
+    {38, 2, K_CONV,    1,  8,  8,  8,  2, 2, 2, 2, 4,  8, 2},
+    {39, 2, K_CONV,    1,  8, 16, 16,  2, 2, 4, 1, 2,  8, 2},
+    {56, 2, K_C16,     1, 16, 16, 16,  4, 1, 4, 1, 1,  2, 4},
+    {57, 2, K_C16,     1, 16, 16, 16,  4, 2, 4, 1, 1,  2, 4},
+};
+constexpr int kNumTilings = sizeof(kTilings) / sizeof(kTilings[0]);
+
+// every row is checked when the table is compiled (what a kernel asserts about its own template arguments is repeated here so that the message names the table)
+template <class P> constexpr bool every_tiling(P ok) {
+    for (int i = 0; i < kNumTilings; ++i)
+        if (!ok(kTilings[i])) return false;
+    return true;
+}
+static_assert(every_tiling([](const Tiling& t) { int n = 0; for (const Tiling& u : kTilings) n += u.id == t.id; return n == 1; }), "two tilings share an id");
+static_assert(every_tiling([](const Tiling& t) { return (t.ndim == 2 || t.ndim == 3) && (t.td == 1) == (t.ndim == 2); }), "a 2-D box is one plane deep, a 3-D box is not");
+static_assert(every_tiling([](const Tiling& t) { return (t.tx == 16 || t.tx == 8 || t.tx == 4) && t.tw % t.tx == 0 && t.th % (16 / t.tx) == 0; }), "box must be cut into whole 16-voxel tiles");
+static_assert(every_tiling([](const Tiling& t) { return t.wm * t.wn == 4 && t.tm * t.wm * 16 == t.td * t.th * t.tw; }), "four waves of tm tiles must cover the box");
+static_assert(every_tiling([](const Tiling& t) { return t.kind == K_CONV || (t.wm == 4 && t.wn == 1 && t.nres == 1 && t.tx == 16); }), "the Cin == 16 kernels fix the wave grid, one chunk and 16-voxel rows");
+static_assert(every_tiling([](const Tiling& t) {
+    const int ntap = t.kd() * 9;            // conv3x_kernel: ring divides the taps; conv3x16_kernel: ring inside the (ntap + 1) / 2 steps; conv3x16r_kernel: all 15 steps
+    return t.pf >= 0 && (t.kind == K_CONV ? ntap % (t.pf + 1) == 0 : (t.kind == K_C16 ? t.pf + 1 <= (ntap + 1) / 2 : t.pf + 1 == 15));
+}), "pf does not fit the tap loop of the kernel");
+
+// boxes of a launch, and its grid: x = boxes (rounded up to the 8 XCDs when remapped, c3x_box_of_block), y = Cout / bn
+inline long long num_boxes(int td, int th, int tw, int N, int D, int H, int W) {
+    return (long long)N * ((D + td - 1) / td) * ((H + th - 1) / th) * ((W + tw - 1) / tw);
+}
+template <class B> dim3 launch_grid(const Conv3xArgs& a, int bn) {
+    const long long nbox = num_boxes(B::TD, B::TH, B::TW, a.N, a.D, a.H, a.W);
+    return dim3(a.remap ? (unsigned)((nbox + 7) / 8 * 8) : (unsigned)nbox, a.Cout / bn);
 }
 
+template <class T, class B, int TM, int TN, int WM, int WN, int NRES, int PF, int OCC>
+void launch_cfg(const Conv3xArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x_kernel<T, B, TM, TN, WM, WN, NRES, PF, OCC>), launch_grid<B>(a, WN * TN * 16), dim3(256), 0, s, a);
+}
 template <class T, class B, int TM, int TN, int PF, int OCC>
 void launch_cfg16(const Conv3xArgs& a, hipStream_t s) {
-    const long long nbox = (long long)a.N * ((a.D + B::TD - 1) / B::TD) * ((a.H + B::TH - 1) / B::TH) * ((a.W + B::TW - 1) / B::TW);
-    dim3 grid(a.remap ? (unsigned)((nbox + 7) / 8 * 8) : (unsigned)nbox, a.Cout / (TN * 16));
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x16_kernel<T, B, TM, TN, PF, OCC>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x16_kernel<T, B, TM, TN, PF, OCC>), launch_grid<B>(a, TN * 16), dim3(256), 0, s, a);
+}
+template <class T, class B, int TM, int TN, int OCC>
+void launch_cfg16r(const Conv3xArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x16r_kernel<T, B, TM, TN, OCC>), launch_grid<B>(a, TN * 16), dim3(256), 0, s, a);
 }
 
-// one translation unit per (dtype, ndim): the tap loops are fully unrolled and each instantiation takes ~10 s to compile
+// row I, if it is an ND-dimensional tiling with this id: its kernel, with the row's constants as template arguments
+template <class T, int ND, int I> bool launch_row(int id, const Conv3xArgs& a, hipStream_t s) {
+    constexpr Tiling t = kTilings[I];
+    if constexpr (t.ndim == ND) {
+        if (id != t.id) return false;
+        using B = XBox<t.td, t.th, t.tw, t.kd(), t.tx>;
+        if constexpr (t.kind == K_CONV) launch_cfg<T, B, t.tm, t.tn, t.wm, t.wn, t.nres, t.pf, t.occ>(a, s);
+        else if constexpr (t.kind == K_C16) launch_cfg16<T, B, t.tm, t.tn, t.pf, t.occ>(a, s);
+        else launch_cfg16r<T, B, t.tm, t.tn, t.occ>(a, s);
+        return true;
+    }
+    return false;
+}
+// every ND-dimensional row of the table for run dtype T (rows = Rows{}); false: no such tiling
+using Rows = std::make_integer_sequence<int, kNumTilings>;
+template <class T, int ND, int... I> bool launch_nd(int id, const Conv3xArgs& a, hipStream_t s, std::integer_sequence<int, I...>) {
+    return (launch_row<T, ND, I>(id, a, s) || ...);
+}
+
+// one translation unit per (dtype, ndim) instantiates launch_nd (conv3x_<dtype>_<nd>.hip): the tap loops are fully unrolled and each kernel takes ~10 s to compile
 template <class T> bool launch_3d(int id, const Conv3xArgs& a, hipStream_t s);
 template <class T> bool launch_2d(int id, const Conv3xArgs& a, hipStream_t s);
-
-/* halo-conv tilings:                  box              TM TN WM WN NRES PF OCC */
-#define SEG_C3X_3D_CONV_CASES                                                                                         \
-        case 0: launch_cfg<T, XBox<2, 8, 16, 3, 16>, 4, 2, 4, 1, 1, 2, 2>(a, s); return true;                         \
-        case 1: launch_cfg<T, XBox<4, 8, 16, 3, 16>, 8, 2, 4, 1, 1, 2, 1>(a, s); return true;                         \
-        case 2: launch_cfg<T, XBox<2, 8, 16, 3, 16>, 8, 2, 2, 2, 2, 8, 1>(a, s); return true;                         \
-        case 3: launch_cfg<T, XBox<2, 8, 8, 3, 8>, 4, 2, 2, 2, 2, 8, 2>(a, s); return true;                           \
-        case 4: launch_cfg<T, XBox<4, 8, 8, 3, 8>, 8, 2, 2, 2, 2, 8, 1>(a, s); return true;                           \
-        case 5: launch_cfg<T, XBox<4, 8, 8, 3, 8>, 4, 4, 4, 1, 2, 2, 1>(a, s); return true;                           \
-        case 6: launch_cfg<T, XBox<2, 8, 8, 3, 8>, 2, 4, 4, 1, 2, 2, 2>(a, s); return true;                           \
-        case 7: launch_cfg<T, XBox<2, 4, 12, 3, 4>, 3, 2, 2, 2, 4, 8, 1>(a, s); return true;                          \
-        case 8: launch_cfg<T, XBox<4, 4, 12, 3, 4>, 6, 2, 2, 2, 4, 8, 1>(a, s); return true;                          \
-        case 9: launch_cfg<T, XBox<2, 4, 12, 3, 4>, 3, 4, 2, 2, 4, 2, 1>(a, s); return true;                          \
-        case 10: launch_cfg<T, XBox<2, 8, 16, 3, 16>, 4, 1, 4, 1, 1, 8, 2>(a, s); return true;                        \
-        case 11: launch_cfg<T, XBox<2, 8, 8, 3, 8>, 4, 2, 2, 2, 4, 8, 1>(a, s); return true;                          \
-        case 12: launch_cfg<T, XBox<2, 8, 8, 3, 8>, 4, 4, 2, 2, 4, 2, 1>(a, s); return true;                          \
-        case 13: launch_cfg<T, XBox<2, 8, 8, 3, 8>, 2, 2, 4, 1, 2, 8, 2>(a, s); return true;                          \
-        case 14: launch_cfg<T, XBox<4, 8, 8, 3, 8>, 4, 2, 4, 1, 1, 2, 2>(a, s); return true;                          \
-        case 15: launch_cfg<T, XBox<2, 8, 16, 3, 16>, 4, 2, 4, 1, 2, 8, 1>(a, s); return true;                        \
-        case 16: launch_cfg<T, XBox<2, 8, 16, 3, 16>, 4, 2, 4, 1, 1, 8, 2>(a, s); return true;                        \
-        case 17: launch_cfg<T, XBox<4, 8, 8, 3, 8>, 4, 2, 4, 1, 1, 8, 2>(a, s); return true;                          \
-        case 20: launch_cfg<T, XBox<4, 8, 8, 3, 8>, 4, 2, 4, 1, 1, 2, 3>(a, s); return true;                          \
-        case 21: launch_cfg<T, XBox<2, 8, 8, 3, 8>, 2, 2, 4, 1, 1, 2, 4>(a, s); return true;                          \
-        case 22: launch_cfg<T, XBox<2, 8, 8, 3, 8>, 2, 2, 4, 1, 1, 8, 3>(a, s); return true;                          \
-        case 23: launch_cfg<T, XBox<4, 8, 8, 3, 8>, 4, 2, 4, 1, 1, 8, 3>(a, s); return true;                          \
-        case 44: launch_cfg<T, XBox<2, 4, 12, 3, 4>, 3, 2, 2, 2, 4, 26, 1>(a, s); return true;                         \
-        case 45: launch_cfg<T, XBox<2, 4, 12, 3, 4>, 3, 1, 2, 2, 4, 26, 1>(a, s); return true;                         \
-        case 46: launch_cfg<T, XBox<2, 4, 12, 3, 4>, 3, 1, 2, 2, 4, 8, 1>(a, s); return true;                          \
-        case 47: launch_cfg<T, XBox<4, 4, 12, 3, 4>, 6, 1, 2, 2, 4, 8, 1>(a, s); return true;                          \
-        case 48: launch_cfg<T, XBox<4, 4, 12, 3, 4>, 6, 1, 2, 2, 4, 26, 1>(a, s); return true;                         \
-        case 49: launch_cfg<T, XBox<2, 4, 12, 3, 4>, 6, 1, 1, 4, 4, 8, 1>(a, s); return true;                          \
-        case 50: launch_cfg<T, XBox<2, 4, 12, 3, 4>, 6, 1, 1, 4, 4, 26, 1>(a, s); return true;      
-/* Cin == 16 tilings (conv3x16_kernel): box             TM TN PF OCC */
-#define SEG_C3X_3D_C16_CASES                                                                                          \
-        case 24: launch_cfg16<T, XBox<2, 8, 16, 3, 16>, 4, 1, 2, 4>(a, s); return true;                               \
-        case 25: launch_cfg16<T, XBox<4, 8, 16, 3, 16>, 8, 1, 2, 3>(a, s); return true;                               \
-        case 26: launch_cfg16<T, XBox<2, 8, 16, 3, 16>, 4, 2, 2, 3>(a, s); return true;                               \
-        case 27: launch_cfg16<T, XBox<4, 8, 16, 3, 16>, 8, 2, 2, 2>(a, s); return true;                               \
-        case 28: launch_cfg16r<T, XBox<2, 8, 16, 3, 16>, 4, 1, 4>(a, s); return true;                                 \
-        case 29: launch_cfg16r<T, XBox<4, 8, 16, 3, 16>, 8, 1, 3>(a, s); return true;
-#define SEG_C3X_3D_BODY switch (id) { SEG_C3X_3D_CONV_CASES SEG_C3X_3D_C16_CASES default: return false; }
-
-#define SEG_C3X_2D_CONV_CASES                                                                                         \
-        case 32: launch_cfg<T, XBox<1, 16, 16, 1, 16>, 4, 2, 4, 1, 1, 8, 2>(a, s); return true;                       \
-        case 33: launch_cfg<T, XBox<1, 16, 16, 1, 16>, 8, 2, 2, 2, 2, 2, 2>(a, s); return true;                       \
-        case 34: launch_cfg<T, XBox<1, 8, 16, 1, 16>, 4, 2, 2, 2, 2, 8, 2>(a, s); return true;                        \
-        case 35: launch_cfg<T, XBox<1, 8, 16, 1, 16>, 4, 2, 2, 2, 4, 8, 2>(a, s); return true;                        \
-        case 36: launch_cfg<T, XBox<1, 8, 16, 1, 16>, 4, 4, 2, 2, 4, 2, 2>(a, s); return true;                        \
-        case 37: launch_cfg<T, XBox<1, 16, 16, 1, 16>, 4, 1, 4, 1, 1, 8, 3>(a, s); return true;                       \
-        case 38: launch_cfg<T, XBox<1, 8, 8, 1, 8>, 2, 2, 2, 2, 4, 8, 2>(a, s); return true;                          \
-        case 39: launch_cfg<T, XBox<1, 8, 16, 1, 16>, 2, 2, 4, 1, 2, 8, 2>(a, s); return true;      
-#define SEG_C3X_2D_C16_CASES                                                                                          \
-        case 56: launch_cfg16<T, XBox<1, 16, 16, 1, 16>, 4, 1, 2, 4>(a, s); return true;                              \
-        case 57: launch_cfg16<T, XBox<1, 16, 16, 1, 16>, 4, 2, 2, 4>(a, s); return true;
-#define SEG_C3X_2D_BODY switch (id) { SEG_C3X_2D_CONV_CASES SEG_C3X_2D_C16_CASES default: return false; }
-
 
 }  // namespace c3x
 }  // namespace seg

@@ -134,7 +134,7 @@ def pack(w, layout, dtype, frag=False):
     layouts: conv_fwd [co][(t,ci)] | conv_dgrad [ci][(flip t,co)] | k2s2_dgrad [(a,ci)][co] |
              convT_fwd [(a,co)][ci] | convT_dgrad [ci][(a,co)]
     frag=True: the same elements in MFMA-fragment-major order (conv3x: layout 1, or 2 for 16 channels); frag=3: the row-reuse layout of the
-    16-channel 3-D tilings 28 .. 31 (seg_op_conv3x_cfg_frag); frag="all": a dict {layout: tensor} of every layout the shape has (conv3x picks by tiling)."""
+    16-channel 3-D tilings for which seg_op_conv3x_cfg_frag(cfg) is 3 (today 28 and 29); frag="all": a dict {layout: tensor} of every layout the shape has (conv3x picks by tiling)."""
     if frag == "all":
         out = {}
         t = pack(w, layout, dtype, frag=True)
@@ -321,7 +321,7 @@ def conv3x_cfgs(device):
 
 def conv3x(x, wfrag, dtype, ndim, cout, bias=None, want_stats=False, out=None, x1=None, cfg=-1):
     """Register-blocked halo conv (16-bit, Cin % 32 == 0 or 16); wfrag = pack(..., frag=True / 3 / "all") in the layout the tiling reads
-    (seg_op_conv3x_cfg_frag; a dict from frag="all" is indexed by it).  x1: second concat source."""
+    (seg_op_conv3x_cfg_frag(cfg): 1, or 2 / 3 for 16 channels; a dict from frag="all" is indexed by it).  x1: second concat source."""
     lib = _capi.lib_for(x.device)
     N, D, H, W, c0 = x.shape
     cin = c0 + (x1.shape[-1] if x1 is not None else 0)
