@@ -672,6 +672,40 @@ int seg_augment3d(const float* x, float* out, int n, int c, int n0, int n1, int 
 int seg_augment3d_shift(float* x, int n, int c, int n0, int n1, int n2, long long xs_c, long long xs_v, const double* params_dev,
                         double rescale, const void* ws, void* stream);
 
+/* ---- Segmenation_Aug (dataprocess/AugData.py of the reference: an albumentations Compose) on the device: a batch of 2-D images and their label images
+ * through per-sample flips, one blur, an affine warp and brightness / contrast in ONE launch (csrc/augment2d.hip).  The arithmetic below IS the contract:
+ * it is not pinned to albumentations / cv2 (neither can run where this library is built and tested, and their draw order and uint8 fixed-point
+ * interpolation differ between their own versions); tests/aug2d_oracle.py restates it in float64.
+ * x / out: f32, n samples of c channels on the grid (h, w); element (s, ch, y, x) of the input lives at s*xs_n + ch*xs_c + (y*w + x)*xs_v, of the output
+ * at s*c*V + ch*xs_c + (y*w + x)*xs_v with V = h*w: (N, C, H, W) is (xs_n, xs_c, xs_v) = (c*V, V, 1), channel-last (N, H, W, C) is (c*V, 1, c).
+ * xs_n == 0: all n outputs are variants of ONE source image (and one source label); otherwise xs_n >= c*V.  out != x.
+ * label / label_out: NULL, or SEG_LABEL_U8 / _I64 / _F32 images [n][h][w] (one channel).
+ * params_dev: device memory, SEG_AUGMENT2D_PARAM_DOUBLES doubles per sample; params_host: the same block in host memory, only validated:
+ *   [0..5] M row-major 2x3   [6] flips (1 horizontal, 2 vertical, or-ed)   [7] warp   [8] blur   [9] k   [10] alpha   [11] beta   [12] clip
+ *   [13] clip_lo   [14] clip_hi   [15] 0 - or weight 48, the last of a 7 x 7 kernel, which 16 + 49 slots would need one more double for
+ *   [16..64) the k*k blur weights row-major (the first 48 of a 7 x 7 kernel), the rest 0
+ * Output pixel (y, x) of a sample, every channel alike:
+ *   1. flip   F(y, x) = src(vflip ? h-1-y : y, hflip ? w-1-x : x)
+ *   2. blur   (image only)  0: G = F.  1: G = correlation of F with the k x k weights (k 3, 5 or 7, anchor at the centre, weights and sum in f32; a tap
+ *             outside the image reads index i folded with period 2(n-1), 0 for n == 1: d c b | a b c d, cv2's BORDER_REFLECT_101).
+ *             2: the 3 x 3 median with replicated edges - a selection, no arithmetic.
+ *   3. warp   skipped when warp == 0 (G passes bit for bit).  sy = (y*M[0][0] + x*M[0][1]) + M[0][2], sx from row 1, in double without fused
+ *             multiply-add.  Image: bilinear over floor(sy), floor(sy)+1 and floor(sx), floor(sx)+1 with f32 weights
+ *             (1-wy)*((1-wx)*g00 + wx*g01) + wy*((1-wx)*g10 + wx*g11); the blur is evaluated at the taps.  Label: the pixel at floor(sy + 0.5),
+ *             floor(sx + 0.5).  border_mode: SEG_AUGMENT_MIRROR folds an index as the blur does, however far out; SEG_AUGMENT_NEAREST clamps it;
+ *             SEG_AUGMENT_CONSTANT gives cval to a tap outside and label_cval to a label pixel outside.  _REFLECT and _WRAP are refused.
+ *   4. tone   (image only)  v = alpha*v + beta in f32 unless alpha == 1 and beta == 0; then clamp to [clip_lo, clip_hi] when clip != 0.
+ * With blur 0 or 2, warp 0, alpha 1, beta 0 and clip 0 every output value is a bit copy of an input value.
+ * ws: seg_augment2d_ws_bytes(n) bytes - 0 today, ws may then be NULL.  Errors (nothing is launched): a null pointer, n outside 1..65535, an extent
+ * below 1 or h*w above 2^31, strides that leave a sample, non-finite M / alpha / beta / cval / weights, blur outside 0..2, k outside {3, 5, 7} when
+ * blur == 1, flips outside 0..3, clip_lo > clip_hi, a refused or unknown border mode, a label_cval an integer label type cannot hold (mode constant),
+ * out == x.  Stream-ordered, no allocation, no readback, no synchronisation; no parameter value can make a read leave the input. */
+enum { SEG_AUGMENT_MIRROR = 4, SEG_AUGMENT2D_PARAM_DOUBLES = 64 };
+long long seg_augment2d_ws_bytes(int n);      /* may return 0 */
+int seg_augment2d(const float* x, float* out, int n, int c, int h, int w, long long xs_n, long long xs_c, long long xs_v,
+                  const void* label, void* label_out, int label_type, const double* params_host, const double* params_dev,
+                  int border_mode, double cval, double label_cval, void* ws, void* stream);
+
 /* ---- mask post-processing (dataprocess/utils.py:7-96 of the reference) on the device (csrc/postproc.hip): connected components and binary morphology
  * of n independent uint8 volumes [n][d][h][w] (2-D: d = 1).  A voxel is foreground when value == cls, or when value != 0 for cls == -1.  Nothing
  * connects or spreads across samples.  Limits: 1 <= d, h, w <= 2048, 1 <= n <= 65535, n*d*h*w < 2^31.

@@ -125,6 +125,8 @@ SIGNATURES = {
     "seg_augment3d_ws_bytes": (_ll, [_i]),
     "seg_augment3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _ll, _ll, _vp, _vp, _i, _i, _vp, _vp, _i, _d, _d, _d, _i, _vp, _vp]),
     "seg_augment3d_shift": (_i, [_vp, _i, _i, _i, _i, _i, _ll, _ll, _vp, _d, _vp, _vp]),
+    "seg_augment2d_ws_bytes": (_ll, [_i]),
+    "seg_augment2d": (_i, [_vp, _vp, _i, _i, _i, _i, _ll, _ll, _ll, _vp, _vp, _i, _vp, _vp, _i, _d, _d, _vp, _vp]),
     "seg_cc_ws_bytes": (_ll, [_i, _i, _i, _i]),
     "seg_cc_label": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "seg_cc_filter": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _ll, _vp, _vp, _vp]),

@@ -283,6 +283,54 @@ int seg_augment3d_shift(float* x, int n, int c, int n0, int n1, int n2, long lon
     return SEG_OK("seg_augment3d_shift");
 }
 
+long long seg_augment2d_ws_bytes(int n) {
+    if (n < 1 || n > 65535) return fail("seg_augment2d_ws_bytes: n must be 1..65535");
+    return 0;
+}
+int seg_augment2d(const float* x, float* out, int n, int c, int h, int w, long long xs_n, long long xs_c, long long xs_v, const void* label,
+                  void* label_out, int label_type, const double* params_host, const double* params_dev, int border_mode, double cval,
+                  double label_cval, void* ws, void* stream) {
+    (void)ws;
+    if (!x || !out || x == out || !params_host || !params_dev || (label != nullptr) != (label_out != nullptr) || (label && label == label_out))
+        return fail("seg_augment2d: null pointer, or a transform in place");
+    if (!augment_extents_ok(n, c, 1, h, w)) return fail("seg_augment2d: n, c must be 1..65535, extents >= 1 with h*w <= 2^31");
+    const long long V = (long long)h * w;
+    if (!augment_strides_ok(c, V, xs_c, xs_v) || (xs_n != 0 && xs_n < (long long)c * V))
+        return fail("seg_augment2d: strides must be positive and stay inside a sample's c*V elements, xs_n 0 or >= c*V");
+    if (border_mode == SEG_AUGMENT_REFLECT || border_mode == SEG_AUGMENT_WRAP)
+        return fail("seg_augment2d: border modes reflect and wrap are not implemented (mirror, nearest and constant are)");
+    if (border_mode != SEG_AUGMENT_MIRROR && border_mode != SEG_AUGMENT_NEAREST && border_mode != SEG_AUGMENT_CONSTANT)
+        return fail("seg_augment2d: unknown border mode");
+    if (label && label_type != LT_U8 && label_type != LT_I64 && label_type != LT_F32) return fail("seg_augment2d: label type must be u8, i64 or f32");
+    if (!std::isfinite(cval) || !std::isfinite(label_cval)) return fail("seg_augment2d: cval must be finite");
+    for (int s = 0; s < n; ++s) {
+        const double* p = params_host + (size_t)s * SEG_AUGMENT2D_PARAM_DOUBLES;
+        for (int k = 0; k < 6; ++k)
+            if (!std::isfinite(p[k])) return fail("seg_augment2d: non-finite matrix");
+        if (!std::isfinite(p[10]) || !std::isfinite(p[11])) return fail("seg_augment2d: non-finite alpha or beta");
+        if (!(p[6] >= 0.0 && p[6] <= 3.0) || p[6] != (double)(int)p[6]) return fail("seg_augment2d: flips must be an integer 0..3");
+        if (!std::isfinite(p[7]) || !std::isfinite(p[12])) return fail("seg_augment2d: non-finite warp or clip switch");
+        if (p[8] != 0.0 && p[8] != 1.0 && p[8] != 2.0) return fail("seg_augment2d: blur must be 0 (none), 1 (weights) or 2 (median)");
+        if (p[8] == 1.0) {
+            if (p[9] != 3.0 && p[9] != 5.0 && p[9] != 7.0) return fail("seg_augment2d: k must be 3, 5 or 7");
+            for (int k = 0; k < (int)(p[9] * p[9]); ++k)
+                if (!std::isfinite(p[k < 48 ? 16 + k : 15])) return fail("seg_augment2d: non-finite blur weight");
+        }
+        if (p[12] != 0.0 && !(p[13] <= p[14])) return fail("seg_augment2d: clip needs clip_lo <= clip_hi");
+    }
+    if (label && border_mode == SEG_AUGMENT_CONSTANT && label_type != LT_F32) {
+        const double lim = label_type == LT_U8 ? 255.0 : 9007199254740992.0;      // (2^53: every integer below is a double)
+        if (label_cval != std::floor(label_cval) || label_cval > lim || label_cval < (label_type == LT_U8 ? 0.0 : -lim))
+            return fail("seg_augment2d: label_cval is not representable in the label type");
+    }
+    Augment2dArgs a = {};
+    a.x = x; a.out = out; a.label = label; a.label_out = label_out; a.params = params_dev;
+    a.N = n; a.C = c; a.H = h; a.W = w; a.V = V; a.xs_n = xs_n; a.xs_c = xs_c; a.xs_v = xs_v; a.ls_n = xs_n == 0 ? 0 : V;
+    a.border = border_mode; a.cval = (float)cval; a.label_cval = label_cval;
+    launch_augment2d(a, label_type, (hipStream_t)stream);
+    return SEG_OK("seg_augment2d");
+}
+
 
 static int postproc_extents_ok(int n, int d, int h, int w) {
     return n >= 1 && n <= 65535 && d >= 1 && h >= 1 && w >= 1 && d <= 2048 && h <= 2048 && w <= 2048 && (long long)n * d * h * w < (1ll << 31);

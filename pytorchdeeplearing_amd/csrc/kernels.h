@@ -317,6 +317,18 @@ void launch_augment3d(Augment3dArgs a, int label_type, void* ws, hipStream_t s);
 // in place: clip(x + (float)params[n][16 + c], min, max) from the workspace when params != nullptr, then * scale when has_scale
 void launch_augment3d_shift(float* x, int N, int C, long long V, long long xs_c, long long xs_v, const double* params, const void* ws, float scale,
                             int has_scale, hipStream_t s);
+// Segmenation_Aug (dataprocess/AugData.py), augment2d.hip: flip, blur, warp and brightness / contrast of a batch of 2-D images and label images in one
+// launch; steps, parameter block and strides as documented at seg_augment2d in include/segengine.h
+constexpr int AUG2D_PARAM_DOUBLES = SEG_AUGMENT2D_PARAM_DOUBLES;
+struct Augment2dArgs {
+    const float* x; float* out;                  // element (s, ch, y, x) = s*xs_n + ch*xs_c + (y*W + x)*xs_v; out: the same with a sample stride of C*V
+    const void* label; void* label_out;          // nullptr, or one channel [N][H][W]
+    const double* params;                        // device, [N][AUG2D_PARAM_DOUBLES]
+    int N, C, H, W;
+    long long V, xs_n, xs_c, xs_v, ls_n;         // xs_n / ls_n: 0 when every sample reads the same source
+    int border; float cval; double label_cval;   // SEG_AUGMENT_MIRROR / _NEAREST / _CONSTANT
+};
+void launch_augment2d(const Augment2dArgs& a, int label_type, hipStream_t s);
 // mask post-processing (dataprocess/utils.py:7-96), postproc.hip: n uint8 volumes [D][H][W], foreground = (value == cls) or (value != 0) for cls == -1;
 // connected components and binary morphology on the bit-packed rows; arguments, stats and workspaces as documented at seg_cc_label / seg_morph3d
 size_t cc_ws_bytes(int n, int d, int h, int w);

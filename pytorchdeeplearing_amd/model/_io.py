@@ -25,6 +25,14 @@ def imread_gray(path):
     return np.asarray(Image.open(path).convert("L"))
 
 
+def imread_color(path):
+    """cv2.imread(path): (H, W, 3) uint8.  cv2 hands out B, G, R and PIL R, G, B; `imwrite` takes what its own reader gave."""
+    if cv2 is not None:
+        return cv2.imread(path)
+    from PIL import Image
+    return np.asarray(Image.open(path).convert("RGB"))
+
+
 def resize(img, size_wh, nearest=False):
     """cv2.resize(img, (w, h)) semantics."""
     if cv2 is not None:

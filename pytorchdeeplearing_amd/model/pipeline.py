@@ -20,7 +20,9 @@ so here:
     GPU that trains ~1000 volumes/s from the page cache (tools/bench_pipeline.py, profiles/r04_pipeline_end_to_end.json).
 
   * `augment=gen` (an `ImageDataGenerator3D`, pytorchdeeplearing_amd/augment.py) transforms every 3-D batch on the device between the upload and the
-    step: the random affine transform, flips, channel shift and rescale of the reference's offline `DataAug3D`, one launch per batch.
+    step: the random affine transform, flips, channel shift and rescale of the reference's offline `DataAug3D`, one launch per batch.  A
+    `Segmenation_Aug` (pytorchdeeplearing_amd/augment2d.py) does the same for 2-D batches (N, C, H, W) with labels (N, H, W); a generator whose
+    dimensionality does not match the batch raises ValueError.
 
 Yields (x float32 (N,C,...) contiguous, y uint8/int64 (N,...) contiguous) on `device`, in DataLoader order."""
 import os
@@ -60,7 +62,7 @@ class _PinnedPool:
 class DevicePrefetcher:
     def __init__(self, loader, device, binary, depth=2, workers=None, augment=None):
         self.loader, self.device, self.binary, self.depth = loader, torch.device(device), binary, max(1, int(depth))
-        self.augment = augment                           # an ImageDataGenerator3D (pytorchdeeplearing_amd/augment.py) or None
+        self.augment = augment                           # an ImageDataGenerator3D (augment.py, 3-D batches), a Segmenation_Aug (augment2d.py, 2-D) or None
         self.cuda = self.device.type == "cuda"
         self.copy_stream = torch.cuda.Stream(self.device) if self.cuda else None
         if workers is None:
@@ -218,11 +220,11 @@ class DevicePrefetcher:
         return (xd, yd) if self.augment is None else self._augment(xd, yd)
 
     def _augment(self, xd, yd):
-        """on-device augmentation of a 3-D batch as it is handed out: one draw per sample in sample order (global np.random, on the consumer's thread),
+        """on-device augmentation of a batch as it is handed out: one draw per sample in sample order (global np.random, on the consumer's thread),
         the parameters staged in a recycled pinned buffer and uploaded without blocking, one gather launch on the consumer's stream.
-        x (N, C, D, H, W): axes 0, 1, 2 of the generator = D, H, W, as DataAug3D maps them."""
+        3-D, x (N, C, D, H, W): axes 0, 1, 2 of the generator = D, H, W, as DataAug3D maps them.  2-D, x (N, C, H, W) with a Segmenation_Aug."""
         from ..augment import PARAM_DOUBLES
-        buf = self.pool.take((xd.shape[0], PARAM_DOUBLES), torch.float64)
+        buf = self.pool.take((xd.shape[0], getattr(self.augment, "PARAM_DOUBLES", PARAM_DOUBLES)), torch.float64)
         xa, ya = self.augment.augment_batch(xd, yd, layout="th", params_buffer=buf)
         ev = None
         if self.cuda:

@@ -39,7 +39,7 @@ class _SegModel(object):
     _focal_gamma = 2
     _mask_scale = 255      # BinaryUNet3dModel.predict returns *1 (modelUnet.py:678)
     _norm3d = "meanstd"    # VNet wrappers z-score (modelVNet.py:681); UNet wrappers use percentile normalize
-    augment = None         # an ImageDataGenerator3D: trainprocess transforms every TRAINING batch on the device (pytorchdeeplearing_amd/augment.py)
+    augment = None         # an ImageDataGenerator3D (3-D wrappers, augment.py) or a Segmenation_Aug (2-D wrappers, augment2d.py): trainprocess transforms every TRAINING batch on the device
     postprocess = None     # callable, device uint8 (D, H, W) -> device uint8 (D, H, W): the 3-D inference / inference_patch / inference_sliding mask on the source grid passes
                            # through it before it leaves the device, e.g. functools.partial(prepost.keep_largest_component) (None changes nothing)
 
