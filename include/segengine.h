@@ -36,7 +36,10 @@
  *   SEG_PACK_SPLIT=0     the weight re-layout as one launch on the caller's stream
  *   SEG_CONV_STREAM=0    the generic implicit-GEMM kernel also where the register-resident streaming conv applies
  *   SEG_WG_DIRECT=0      1^d-conv weight gradients through wgrad_kernel instead of the multi-step streaming kernel
- *   SEG_W3_BOX16=0|2     the 4 x 8 x 16-box weight gradient of the 16-channel level: off / forced onto small volumes (operator tests)
+ *   SEG_WG_S2=0|2        (read per launch) weight gradients of the 2^d stride-2 windows on 16-bit tensors (down-convolutions, ConvTranspose up-convolutions;
+ *                        fine extents twice the coarse ones, 32 x 16 tile): 0 = wgrad_kernel, 2 = the multi-step streaming wgrad_s2_kernel on wgrad_kernel's
+ *                        voxel slices (bit-identical results), default = wgrad_s2_kernel on fewer, longer slices (other order of the fp32 slice sums)
+ *   SEG_W3_BOX16=0|2    the 4 x 8 x 16-box weight gradient of the 16-channel level: off / forced onto small volumes (operator tests)
  *   SEG_C3X_MAP="cin:cout:w=id,..."   per-shape halo-conv tiling override (tools/tune_conv3x.py)
  *   SEG_C3X16_REUSE=0    the 16 -> 16 channel 3-D halo convs through conv3x16_kernel (one LDS fragment read per MFMA, weight layout 2) instead of
  *                        conv3x16r_kernel (fragments reused across the kh taps, weight layout 3) - bit-identical on integer data
@@ -417,6 +420,10 @@ typedef struct seg_wgrad_args {
 } seg_wgrad_args;
 long long seg_op_wgrad_partial_bytes(const seg_wgrad_args* a);
 int seg_op_wgrad(const seg_wgrad_args* a, float* partial_scratch, int dtype, void* stream);
+/* which kernel seg_op_wgrad runs for these arguments now (SEG_WG_S2 is read per call): 0 = wgrad_kernel (voxel gather, one 32-row step in flight),
+ * 1 = wgrad_direct_kernel (1^d stride-1 convs on 16-bit tensors), 2 = wgrad_s2_kernel (2^d stride-2 windows on 16-bit tensors, fine extents twice the
+ * coarse ones, one source, P a multiple of 32, Q = 16) */
+int seg_op_wgrad_kernel(const seg_wgrad_args* a, int dtype);
 
 /* weight re-layout: dst[r1][r2][t][c] (dtype, row length Kpad, zero padded) = src[r1*s1+r2*s2+t'*sT+c*sC],
  * t' = flipT ? T-1-t : t.  `descs` is a DEVICE array. */

@@ -82,6 +82,7 @@ SIGNATURES = {
     "seg_op_conv_kernel": (_i, [_vp]),
     "seg_op_wgrad": (_i, [_vp, _vp, _i, _vp]),
     "seg_op_wgrad_partial_bytes": (_ll, [_vp]),
+    "seg_op_wgrad_kernel": (_i, [_vp, _i]),
     "seg_op_pack": (_i, [_vp, _i, _ll, _i, _vp]),
     "seg_op_conv3": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "seg_op_conv3x": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

@@ -426,6 +426,7 @@ int seg_op_wgrad(const seg_wgrad_args* a, float* partial_scratch, int dtype, voi
     launch_wgrad(*a, partial_scratch, dtype, (hipStream_t)stream);
     return SEG_OK("seg_op_wgrad");
 }
+int seg_op_wgrad_kernel(const seg_wgrad_args* a, int dtype) { return a ? wgrad_kernel_id(*a, dtype) : -1; }
 int seg_op_pack(const seg_pack_desc* descs, int ndesc, long long max_elems, int dtype, void* stream) {
     if (!descs || ndesc < 1) return fail("seg_op_pack: no descriptors");
     launch_pack(descs, ndesc, (int)max_elems, dtype, (hipStream_t)stream);

@@ -33,24 +33,24 @@ __device__ __forceinline__ RowCoord decode_row(long long m64, int D, int H, int 
     return r;
 }
 
-template <class T> struct TFrag {
+template <class T, int LD = LDW> struct TFrag {                // LD: leading dimension of the LDS tile, elements
     static __device__ __forceinline__ typename Mma<T>::frag load(const T* tile, int col0, int lane) {
         const int t = lane & 15, q = lane >> 4;
-        const T* p0 = tile + (4 * q + (t >> 2)) * LDW + col0 + (t & 3) * 4;
+        const T* p0 = tile + (4 * q + (t >> 2)) * LD + col0 + (t & 3) * 4;
         const s16x4 lo = lds_read_tr16(p0);
-        const s16x4 hi = lds_read_tr16(p0 + 16 * LDW);
+        const s16x4 hi = lds_read_tr16(p0 + 16 * LD);
         vec<short, 8> v;
 #pragma unroll
         for (int j = 0; j < 4; ++j) { v[j] = lo[j]; v[4 + j] = hi[j]; }
         return __builtin_bit_cast(typename Mma<T>::frag, v);
     }
 };
-template <> struct TFrag<float> {
+template <int LD> struct TFrag<float, LD> {
     static __device__ __forceinline__ Mma<float>::frag load(const float* tile, int col0, int lane) {
         const int t = lane & 15, q = lane >> 4;
         Mma<float>::frag f;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = tile[(4 * j + q) * LDW + col0 + t];
+        for (int j = 0; j < 8; ++j) f[j] = tile[(4 * j + q) * LD + col0 + t];
         return f;
     }
 };
@@ -393,6 +393,119 @@ __global__ __launch_bounds__(256) void wgrad_direct_kernel(WgradArgs a, WgPlan p
     }
 }
 
+// The 2^d stride-2 windows on 16-bit tensors (down-convolutions and, with the roles of the tensors swapped, the ConvTranspose up-convolutions of
+// networks/VNet3d.py / Unet3d.py) whose fine extents are exactly twice the coarse ones: the windows tile the fine tensor, no tap leaves it, so the kernel
+// is a pure stream too - 113 MB + 28 MB at 96^3 -> 48^3 - that wgrad_kernel<.., 8> ran at 1.0 TB/s with ONE 32-row step (10 KB) in flight per workgroup,
+// a quarter of the threads issuing the x pieces and a decode_row plus bounds test per piece and tap (profiles/r08_trace_timeline.txt: 146.6 us).
+// Here a staging step is 128 coarse rows: a thread owns rows (tid / 4) and (tid / 4) + 64 of the step and the 16-byte piece (tid % 4) of their 64-byte
+// runs - the 32 dR channels of a row, and per (kd, kh) pair the two kw taps x 16 channels that lie next to each other in the fine tensor (a wave reads
+// 16 consecutive coarse voxels = 1 KB contiguous per pair).  One decode_row per row gives the window's base; the taps are constant offsets from it.
+// DEPTH steps (40 KB each with 8 taps) travel in statically indexed register sets as in wgrad_direct_kernel.  A step may straddle w-rows, planes and
+// samples: every row is decoded on its own.  Same partial-tile layout and (CHAIN form) the same 32-row fp32 accumulation order as wgrad_kernel:
+// bit-identical partial tiles for the same slice plan.  Tile: 32 (p) x 16 (q); NT taps (8: 3-D, 4: 2-D) in canonical order t = (kd, kh, kw), kw fastest.
+#ifndef SEG_WG_S2_DEPTH
+#define SEG_WG_S2_DEPTH 2     // register sets of the ring: 2 beat 3 at every shape (tools/build_variant.py -DSEG_WG_S2_DEPTH=n)
+#endif
+// CHAIN: the accumulators run through the 32-row MFMA steps of the slice as in wgrad_kernel (SEG_WG_S2=2, the bit-identity form).  The own, longer slices
+// (28 or more MFMA steps where wgrad_kernel has 1 .. 14) would lengthen that fp32 chain - measured against float64 on the host checker, whose MFMA is a
+// sequential fmaf chain, the error of dW grew 4.5 x - so there every 32-row product starts from zero, the four of a 128-row step are
+// summed pairwise and the step sums are added to the accumulators: no chain longer than the steps of a slice.
+template <class T, int NT, int DEPTH, bool CHAIN>
+__global__ __launch_bounds__(256) void wgrad_s2_kernel(WgradArgs a, WgPlan pl, float* partial) {
+    constexpr int WMT = 128, TP = 32, TQ = 16, LDD = TP + 8, LDX = TQ + 8;
+    constexpr int NG = NT / 2;                                   // (kd, kh) pairs
+    constexpr int MAXW = NT / 2;                                 // 16x16 tiles per wave: 2 NT tiles over 4 waves
+    __shared__ T Ds[WMT * LDD];
+    __shared__ T Xs[NT * WMT * LDX];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int p0 = (int)blockIdx.x * TP;
+    const int M = a.N * a.OD * a.OH * a.OW;                      // (below 2^31: wgrad_s2_eligible)
+    const int mbeg = (int)((long long)blockIdx.y * pl.Mc);
+    const int mend = (mbeg + pl.Mc < M) ? (int)(mbeg + pl.Mc) : M;
+    f32x4 acc[MAXW];
+#pragma unroll
+    for (int i = 0; i < MAXW; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int r0 = tid >> 2, c = tid & 3;                        // rows r0 and r0 + 64 of a step; 16-byte piece c of their 64-byte runs
+    const T* dbase = (const T*)a.dr + p0 + c * 8;
+    const T* xbase = (const T*)a.x0 + c * 8;
+    long long goff[NG];                                          // element offset of pair g's run from the window's base (uniform)
+#pragma unroll
+    for (int g = 0; g < NG; ++g) goff[g] = ((long long)a.taps.d[2 * g] * a.IH + a.taps.h[2 * g]) * a.IW * TQ;
+    int OD = a.OD, OH = a.OH, OW = a.OW;
+    settle(OD); settle(OH); settle(OW);                          // (the divisions stay in the loop instead of hoisted magic numbers in VGPRs)
+    vec<T, 8> dq[DEPTH][2], xq[DEPTH][NG][2];
+    unsigned okq[DEPTH];                                         // bit u: row r0 + 64 u of that set lies inside the slice
+    auto issue = [&](int slot, int ms) {                         // rows past the slice read a valid (clamped) row and are zeroed on the way to LDS
+        const T* dsrc[2];
+        const T* xsrc[2];
+        unsigned ok = 0u;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int m = ms + r0 + 64 * u;
+            const bool v = m < mend;
+            ok |= v ? (1u << u) : 0u;
+            const int mc = v ? m : mbeg;
+            const RowCoord r = decode_row(mc, OD, OH, OW);
+            const long long vox = (((long long)r.n * a.ID + r.d * a.sd) * a.IH + r.h * a.sh) * a.IW + r.w * a.sw;
+            dsrc[u] = dbase + (long long)mc * a.P;
+            xsrc[u] = xbase + vox * TQ;
+        }
+        okq[slot] = ok;
+        __builtin_amdgcn_sched_barrier(0);                       // every address first, then the loads back to back
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            dq[slot][u] = load8(dsrc[u]);
+#pragma unroll
+            for (int g = 0; g < NG; ++g) xq[slot][g][u] = load8(xsrc[u] + goff[g]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+#pragma unroll
+    for (int k = 0; k < DEPTH - 1; ++k) issue(k, mbeg + k * WMT);
+    for (int ms = mbeg; ms < mend; ms += DEPTH * WMT) {
+#pragma unroll
+        for (int k = 0; k < DEPTH; ++k) {
+            // every body runs, also past the end of the slice (zero tiles: exact zeros are added) - see wgrad_direct_kernel
+            issue((k + DEPTH - 1) % DEPTH, ms + (k + DEPTH - 1) * WMT);
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const bool v = (okq[k] >> u) & 1u;
+                const int row = r0 + 64 * u;
+                store8(&Ds[row * LDD + c * 8], v ? dq[k][u] : zero8<T>());
+#pragma unroll
+                for (int g = 0; g < NG; ++g) store8(&Xs[((2 * g + (c >> 1)) * WMT + row) * LDX + (c & 1) * 8], v ? xq[k][g][u] : zero8<T>());
+            }
+            __syncthreads();
+            // wave wv: p-half (wv & 1), taps (wv >> 1) * MAXW ..; one dR fragment feeds MAXW MFMAs
+            const int pi = wv & 1, tb = (wv >> 1) * MAXW;
+            f32x4 part[CHAIN ? 1 : MAXW][CHAIN ? 1 : WMT / 32];
+#pragma unroll
+            for (int kk = 0; kk < WMT / 32; ++kk) {
+                const typename Mma<T>::frag af = TFrag<T, LDD>::load(Ds + kk * 32 * LDD, pi * 16, lane);
+#pragma unroll
+                for (int i = 0; i < MAXW; ++i) {
+                    const typename Mma<T>::frag bf = TFrag<T, LDX>::load(Xs + ((tb + i) * WMT + kk * 32) * LDX, 0, lane);
+                    if constexpr (CHAIN) acc[i] = Mma<T>::run(af, bf, acc[i]);
+                    else part[i][kk] = Mma<T>::run(af, bf, f32x4{0.f, 0.f, 0.f, 0.f});
+                }
+            }
+            if constexpr (!CHAIN) {
+#pragma unroll
+                for (int i = 0; i < MAXW; ++i) acc[i] += (part[i][0] + part[i][1]) + (part[i][2] + part[i][3]);
+            }
+            __syncthreads();
+        }
+    }
+    const int l15 = lane & 15, q = lane >> 4;
+    const int pi = wv & 1, tb = (wv >> 1) * MAXW;
+    float* dst = partial + (long long)blockIdx.y * a.P * NT * TQ;
+#pragma unroll
+    for (int i = 0; i < MAXW; ++i) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dst[((long long)(p0 + pi * 16 + 4 * q + r) * NT + tb + i) * TQ + l15] = acc[i][r];
+    }
+}
+
 // dw[p*sP + q*sQ + tap*sT] += sum_slices partial[slice][p][tap][q]    (stem: column q = (tap, ci))
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* partial, float* dw, int P, int Tn, int Qc, int parts, long long sP,
                                                            long long sQ, long long sT, int stem_cimg, int qreal) {
@@ -451,18 +564,73 @@ WgPlan make_plan(const WgradArgs& a) {
     return pl;
 }
 
+// ---- wgrad_s2_kernel: who may use it, and its slices
+#ifndef SEG_WG_S2_WGS
+#define SEG_WG_S2_WGS 512     // slices aimed at (two resident workgroups per CU) and ...
+#endif
+#ifndef SEG_WG_S2_MINSTEPS
+#define SEG_WG_S2_MINSTEPS 7  // ... the shortest slice in 128-row steps (the ring goes round more than twice); both chosen by the A/B of DESIGN.md 7.3
+#endif
+bool wgrad_s2_eligible(const WgradArgs& a, int elem_size) {
+    if (elem_size != 2 || a.stem || a.act_scale || a.act_shift || a.x1 || a.C1) return false;
+    const int T = a.taps.n;
+    if (T != 8 && T != 4) return false;
+    const bool d3 = T == 8;
+    for (int t = 0; t < T; ++t)                          // the taps are {0,1}^ndim in canonical order (kw fastest): taps 2g, 2g + 1 are neighbours in memory
+        if (a.taps.d[t] != (d3 ? t >> 2 : 0) || a.taps.h[t] != ((t >> 1) & 1) || a.taps.w[t] != (t & 1)) return false;
+    if (a.sd != (d3 ? 2 : 1) || a.sh != 2 || a.sw != 2) return false;
+    if (d3 ? a.ID != 2 * a.OD : (a.ID != 1 || a.OD != 1)) return false;
+    if (a.IH != 2 * a.OH || a.IW != 2 * a.OW) return false;
+    if (a.P % 32 || a.Q != 16 || a.C0 != 16) return false;                               // the 32 x 16 tile
+    const long long fine = (long long)a.N * a.ID * a.IH * a.IW;
+    return a.N > 0 && a.OD > 0 && a.OH > 0 && a.OW > 0 && fine < (1ll << 31) - (1 << 16);  // 32-bit row arithmetic, with room for the steps past a slice
+}
+// 0: off, 1: own slicing, 2: wgrad_kernel's slicing (bit-identical partial tiles).  Read per launch: an operator-level A/B runs in one process.
+int wgrad_s2_mode() { return knob_i("SEG_WG_S2", 1); }
+// the slices of wgrad_s2_kernel: `base` is make_plan()'s plan (whose slice count sizes the partial buffer: never more slices than that)
+WgPlan wgrad_s2_plan(const WgradArgs& a, WgPlan base, int mode) {
+    base.ntile = a.P / 32; base.ntq = 1; base.ntg = 1;
+    if (mode == 2) return base;
+    const long long M = (long long)a.N * a.OD * a.OH * a.OW;
+    long long wgs = SEG_WG_S2_WGS / base.ntile;
+    if (wgs < 1) wgs = 1;
+    long long steps = (M + 128 * wgs - 1) / (128 * wgs);
+    if (steps < SEG_WG_S2_MINSTEPS) steps = SEG_WG_S2_MINSTEPS;
+    long long parts = (M + 128 * steps - 1) / (128 * steps);
+    if (parts > base.parts) parts = base.parts;
+    base.Mc = (M + parts - 1) / parts;                 // even slices: no short last one; the last step of every slice may be ragged
+    base.parts = (int)((M + base.Mc - 1) / base.Mc);
+    return base;
+}
+bool wgrad_direct_on() {
+    static const bool on = (knob_i("SEG_WG_DIRECT", 1) != 0);       // A/B switch
+    return on;
+}
+// the (NPD, NPX, DEPTH) instantiation of wgrad_direct_kernel for this launch as 100 * NPD + 10 * NPX + DEPTH (three steps in flight for the 64-wide q-tiles,
+// else four); 0: none
+int wgrad_direct_key(const WgradArgs& a, const WgPlan& pl, int elem_size) {
+    if (elem_size != 2 || !(wgrad_direct_on() || a.act_scale) || a.stem || pl.TB != 1 || !pl.direct || pl.ntg != 1 || a.C0 % 8) return 0;
+    const int np = pl.TP % 16 ? 0 : pl.TP / 16, nq = pl.TQ % 16 ? 0 : pl.TQ / 16;
+    const int key = 100 * np + 10 * nq + (nq == 4 ? 3 : 4);
+    return (key == 124 || key == 243 || key == 443 || key == 114 || key == 224) ? key : 0;
+}
+
 template <class T>
 void wgrad_dispatch(const WgradArgs& a, float* partial, hipStream_t s, int qreal) {
-    const WgPlan pl = make_plan(a);
+    WgPlan pl = make_plan(a);
     dim3 grid(pl.ntg * pl.ntile, pl.parts);
-    static const bool direct_on = (knob_i("SEG_WG_DIRECT", 1) != 0);       // A/B switch
     bool done = false;
     if constexpr (sizeof(T) == 2) {
-        if ((direct_on || a.act_scale) && !a.stem && pl.TB == 1 && pl.direct && pl.ntg == 1 && a.C0 % 8 == 0) {
-            // the (NPD, NPX, DEPTH) instantiations that exist, as 100 * NPD + 10 * NPX + DEPTH (three steps in flight for the 64-wide q-tiles, else four);
-            // any other tile: not done
-            const int np = pl.TP % 16 ? 0 : pl.TP / 16, nq = pl.TQ % 16 ? 0 : pl.TQ / 16;
-            done = by_int<124, 243, 443, 114, 224>(100 * np + 10 * nq + (nq == 4 ? 3 : 4), [&](auto k) { by_bool(a.act_scale != nullptr, [&](auto act) {
+        const int s2 = wgrad_s2_mode();
+        if (s2 && wgrad_s2_eligible(a, sizeof(T))) {
+            pl = wgrad_s2_plan(a, pl, s2);
+            grid = dim3(pl.ntile, pl.parts);
+            by_int<8, 4>(a.taps.n, [&](auto nt) { by_bool(s2 == 2, [&](auto chain) {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad_s2_kernel<T, nt(), SEG_WG_S2_DEPTH, chain()>), grid, dim3(256), 0, s, a, pl, partial);
+            }); });
+            done = true;
+        } else if (const int key = wgrad_direct_key(a, pl, sizeof(T))) {
+            done = by_int<124, 243, 443, 114, 224>(key, [&](auto k) { by_bool(a.act_scale != nullptr, [&](auto act) {
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad_direct_kernel<T, k() / 100, k() / 10 % 10, k() % 10, act()>), grid, dim3(256), 0, s, a, pl, partial);
             }); });
         }
@@ -497,6 +665,13 @@ bool wgrad_act_supported(const WgradArgs& a) {
 size_t wgrad_partial_bytes(const WgradArgs& a) {
     const WgPlan pl = make_plan(a);
     return (size_t)pl.parts * a.P * (a.stem ? 1 : a.taps.n) * a.Q * sizeof(float);
+}
+
+// which kernel launch_wgrad runs for these arguments (the same predicates as wgrad_dispatch)
+int wgrad_kernel_id(const WgradArgs& a, int dtype) {
+    const int es = dtype == DT_F32 ? 4 : 2;
+    if (wgrad_s2_mode() && wgrad_s2_eligible(a, es)) return 2;
+    return wgrad_direct_key(a, make_plan(a), es) ? 1 : 0;
 }
 
 void launch_wgrad(const WgradArgs& a, float* partial, int dtype, hipStream_t s, int qreal) {

@@ -247,9 +247,14 @@ def conv(x0, wpacked, dtype, ndim, k, stride=1, pad=0, x1=None, bias=None, cout=
     return (out, stats.sum(0)) if want_stats else out
 
 
-def wgrad(dr, x0, dtype, ndim, k, stride=1, pad=0, x1=None, stem=False, act=None):
+last_wgrad_kernel = None
+
+
+def wgrad(dr, x0, dtype, ndim, k, stride=1, pad=0, x1=None, stem=False, act=None, with_partial=False):
     """dW[p][q][tap] (PyTorch conv-weight layout (P, Q, k..)) = sum_m dr[m][p] * x[vox(m,tap)][q].
-    act = (scale, shift), fp32 [N, C0]: x0 is read as relu(scale * x0 + shift) rounded to dtype (1^d convs on 16-bit tensors only)."""
+    act = (scale, shift), fp32 [N, C0]: x0 is read as relu(scale * x0 + shift) rounded to dtype (1^d convs on 16-bit tensors only).
+    with_partial: returns (dW, the fp32 scratch of seg_op_wgrad_partial_bytes: the per-slice partial tiles [slice][P][tap][Q]; slices the launch did not
+    use hold NaN)."""
     lib = _capi.lib_for(dr.device)
     N, OD, OH, OW, P = dr.shape
     _, D, H, W, C0 = x0.shape
@@ -269,8 +274,12 @@ def wgrad(dr, x0, dtype, ndim, k, stride=1, pad=0, x1=None, stem=False, act=None
     dw = _alloc((P, qc) + (k,) * ndim, torch.float32, dr.device, zero=True)
     a.dw = dw.data_ptr()
     scratch = aligned_empty(lib.seg_op_wgrad_partial_bytes(C.byref(a)), dr.device)
+    if with_partial:
+        scratch.view(torch.float32).fill_(float("nan"))
+    global last_wgrad_kernel
+    last_wgrad_kernel = lib.seg_op_wgrad_kernel(C.byref(a), _capi.DTYPE[dtype])      # 0: wgrad_kernel, 1: wgrad_direct_kernel, 2: wgrad_s2_kernel
     lib.check(lib.seg_op_wgrad(C.byref(a), scratch.data_ptr(), _capi.DTYPE[dtype], _capi.stream_for(dr.device)), "seg_op_wgrad")
-    return dw
+    return (dw, scratch.view(torch.float32)) if with_partial else dw
 
 
 def conv3(x, wpacked, dtype, ndim, cout, bias=None, want_stats=False, out=None):
