@@ -748,6 +748,45 @@ long long seg_morph3d_ws_bytes(int n, int d, int h, int w);
 int seg_morph3d(const unsigned char* mask, unsigned char* out, int n, int d, int h, int w, int cls, int op, int shape, int rz, int ry, int rx,
                 int border, int fg_value, void* ws, void* stream);
 
+/* ---- exact Euclidean distance transform (csrc/edt.hip) of n independent uint8 volumes [n][d][h][w] (2-D: d = 1), and the boundary loss that consumes
+ * its maps (Kervadec et al., "Boundary loss for highly unbalanced segmentation").  A voxel is foreground when label == cls, or when label != 0 for
+ * cls == -1 (seg_cc_label's convention).
+ *
+ * seg_edt.  For every foreground voxel the Euclidean distance to the nearest background voxel OF THE SAME SAMPLE, with the spacing (sz, sy, sx) of the
+ * (d, h, w) axes; background voxels get 0; nothing outside the volume counts as background (scipy.ndimage.distance_transform_edt's convention, not the
+ * morphology's border).  The transform is exact, separable and linear in the voxel count: axis x from the bit-packed rows, axes y and z as lower
+ * envelopes of parabolas; no radius, no approximation.  Squared distances come from integer index differences.  With unit spacing the whole computation
+ * is integer (d^2 <= 3 * 2047^2 < 2^24): the f32 stored is the exact integer and the root is correctly rounded.  Otherwise the spacings are rounded to
+ * f32 once, d^2 = sum_a (delta_a * s_a)^2 in f32, and the minimum is taken over true candidates.
+ * mode: SEG_EDT_SQUARED / SEG_EDT_DISTANCE  d^2 / d on the foreground, 0 on the background;
+ *       SEG_EDT_SIGNED    + distance to the foreground outside the mask, - distance to the background inside (two transforms, of the mask and of its
+ *                         complement, in one call);
+ *       SEG_EDT_BOUNDARY  Kervadec's map as published, edt(~m) * [~m] - (edt(m) - 1) * [m]; the "- 1" is taken as written, whatever the spacing.
+ * Samples without a boundary: SQUARED / DISTANCE give +inf on every voxel of a sample with no background voxel (and 0 everywhere on one with no
+ * foreground); SIGNED / BOUNDARY give an all-zero map for a sample whose mask is empty OR full (Kervadec's `if posmask.any()`, extended to the full mask).
+ * out: f32, sample s at out + s * out_stride_n, d*h*w values each; out_stride_n >= d*h*w is the number of floats between consecutive samples, so class k
+ * of every sample can be written straight into plane k of an [n][c][d*h*w] tensor.  Nothing else of `out` is touched.
+ * ws: seg_edt_ws_bytes() bytes, 256-byte aligned: 12 bytes per voxel (two value planes and the envelope stacks) + 8 bytes per 64-voxel row word + 4 per sample.
+ * Limits: 1 <= n <= 65535, 1 <= d, h, w <= 2048, d*h*w < 2^31, cls -1..255, finite spacings > 0.
+ *
+ * seg_boundary_loss.  logits, dist: f32 [n][c][v].  p = sigmoid (c == 1) or softmax over c (c > 1) of the logits in f32;
+ * out1[0] = (1 / M) * sum over samples, planes k >= first_class and voxels of p * dist, M = n * (c - first_class) * v (the mean over the selected planes:
+ * SurfaceLoss with idc = range(first_class, c)).  The products are accumulated in double in a fixed order (per-workgroup partials, then one fold in
+ * index order).  dlogits: NULL, or [n][c][v] that receives grad_scale * d loss / d logit, the Jacobian of the sigmoid / softmax included, in the same
+ * pass: c == 1: p (1 - p) dist / M;  c > 1: p_j ([j >= first_class] dist_j - sum_{k >= first_class} p_k dist_k) / M.
+ * ws: seg_boundary_loss_ws_bytes() bytes.  Limits: n >= 1, v >= 1, 1 <= c <= 16, 0 <= first_class < c.
+ *
+ * Both calls: stream-ordered, no allocation, no host synchronisation, no grid that depends on the data, no floating-point atomics - two calls on the same
+ * input agree bit for bit.  Errors (nothing is launched, seg_last_error() says which): null pointers (dlogits excepted), limits, a spacing that is not a
+ * finite positive number, an unknown mode, out_stride_n < d*h*w. */
+enum { SEG_EDT_SQUARED = 0, SEG_EDT_DISTANCE = 1, SEG_EDT_SIGNED = 2, SEG_EDT_BOUNDARY = 3 };
+long long seg_edt_ws_bytes(int n, int d, int h, int w);
+int seg_edt(const unsigned char* labels, int n, int d, int h, int w, int cls, double sz, double sy, double sx, int mode, void* ws,
+            float* out, long long out_stride_n, void* stream);
+long long seg_boundary_loss_ws_bytes(int n, int c, long long v);
+int seg_boundary_loss(const float* logits, const float* dist, int n, int c, long long v, int first_class, float grad_scale, void* ws,
+                      float* out1, float* dlogits, void* stream);
+
 /* ---- measurement: HIP-event timing of kernel classes inside a running forward/backward.
  * seg_profile_enable(h, mask): from now on every launch whose class bit is set in `mask` is
  * bracketed by hipEventRecord on the launch stream (0 disables).  seg_profile_read(h, ...)

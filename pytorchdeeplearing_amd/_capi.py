@@ -133,6 +133,10 @@ SIGNATURES = {
     "seg_cc_filter": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _ll, _vp, _vp, _vp]),
     "seg_morph3d_ws_bytes": (_ll, [_i, _i, _i, _i]),
     "seg_morph3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "seg_edt_ws_bytes": (_ll, [_i, _i, _i, _i]),
+    "seg_edt": (_i, [_vp, _i, _i, _i, _i, _i, _d, _d, _d, _i, _vp, _vp, _ll, _vp]),
+    "seg_boundary_loss_ws_bytes": (_ll, [_i, _i, _ll]),
+    "seg_boundary_loss": (_i, [_vp, _vp, _i, _i, _ll, _i, _f, _vp, _vp, _vp, _vp]),
     "seg_op_resample3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, _d, _d, _i, _vp]),
     "seg_op_normalize_ws_bytes": (_ll, []),
     "seg_op_normalize_meanstd": (_i, [_vp, _vp, _ll, _i, _f, _f, _vp, _vp]),

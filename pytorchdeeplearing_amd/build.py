@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libsegengine.so")
-SRCS = ["conv.hip", "conv3.hip", "conv3x.hip", "conv3x_f16_3d.hip", "conv3x_f16_2d.hip", "conv3x_bf16_3d.hip", "conv3x_bf16_2d.hip", "wgrad.hip", "stemx.hip", "norm.hip", "misc.hip", "cls_head.hip", "gradcam.hip", "lovasz.hip", "ssim.hip", "cldice.hip", "surface.hip", "augment.hip", "augment2d.hip", "postproc.hip", "prepost.hip", "sliding.hip", "engine.hip", "engine_plan.hip", "capi_ops.hip"]
+SRCS = ["conv.hip", "conv3.hip", "conv3x.hip", "conv3x_f16_3d.hip", "conv3x_f16_2d.hip", "conv3x_bf16_3d.hip", "conv3x_bf16_2d.hip", "wgrad.hip", "stemx.hip", "norm.hip", "misc.hip", "cls_head.hip", "gradcam.hip", "lovasz.hip", "ssim.hip", "cldice.hip", "surface.hip", "augment.hip", "augment2d.hip", "postproc.hip", "edt.hip", "prepost.hip", "sliding.hip", "engine.hip", "engine_plan.hip", "capi_ops.hip"]
 # every project header: the build id and the freshness checks cover all of them (tests/emu/build_emu.py uses the same list)
 HDRS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(os.path.dirname(HERE), "include", "segengine.h")]
 ID_UNIT = "engine.hip"          # compiled with -DSEG_BUILD_ID

@@ -378,6 +378,42 @@ int seg_morph3d(const unsigned char* mask, unsigned char* out, int n, int d, int
     return SEG_OK("seg_morph3d");
 }
 
+static int edt_extents_ok(int n, int d, int h, int w) {
+    return n >= 1 && n <= 65535 && d >= 1 && h >= 1 && w >= 1 && d <= 2048 && h <= 2048 && w <= 2048 && (long long)d * h * w < (1ll << 31);
+}
+static const char* const EDT_EXTENTS = "n must be 1..65535, extents 1..2048 with d*h*w < 2^31";
+long long seg_edt_ws_bytes(int n, int d, int h, int w) {
+    if (!edt_extents_ok(n, d, h, w)) return fail(std::string("seg_edt_ws_bytes: ") + EDT_EXTENTS);
+    return (long long)edt_ws_bytes(n, d, h, w);
+}
+int seg_edt(const unsigned char* labels, int n, int d, int h, int w, int cls, double sz, double sy, double sx, int mode, void* ws, float* out,
+            long long out_stride_n, void* stream) {
+    if (!labels || !ws || !out) return fail("seg_edt: null pointer");
+    if (!edt_extents_ok(n, d, h, w)) return fail(std::string("seg_edt: ") + EDT_EXTENTS);
+    if (cls < -1 || cls > 255) return fail("seg_edt: cls must be -1 (label != 0) or a label value 0..255");
+    const float fz = (float)sz, fy = (float)sy, fx = (float)sx;       // rounded once; what the kernels compute with
+    if (!(std::isfinite(fz) && std::isfinite(fy) && std::isfinite(fx) && fz > 0.f && fy > 0.f && fx > 0.f))
+        return fail("seg_edt: spacings must be finite and positive (as f32)");
+    if (mode < SEG_EDT_SQUARED || mode > SEG_EDT_BOUNDARY) return fail("seg_edt: unknown mode");
+    if (out_stride_n < (long long)d * h * w) return fail("seg_edt: out_stride_n must be at least d*h*w");
+    launch_edt(labels, n, d, h, w, cls, fz, fy, fx, mode, ws, out, out_stride_n, (hipStream_t)stream);
+    return SEG_OK("seg_edt");
+}
+static int boundary_loss_extents_ok(int n, int c, long long v) { return n >= 1 && v >= 1 && c >= 1 && c <= 16; }
+long long seg_boundary_loss_ws_bytes(int n, int c, long long v) {
+    if (!boundary_loss_extents_ok(n, c, v)) return fail("seg_boundary_loss_ws_bytes: classes must be 1..16, batch and volume non-empty");
+    return (long long)boundary_loss_ws_bytes();
+}
+int seg_boundary_loss(const float* logits, const float* dist, int n, int c, long long v, int first_class, float grad_scale, void* ws, float* out1,
+                      float* dlogits, void* stream) {
+    if (!logits || !dist || !ws || !out1) return fail("seg_boundary_loss: null pointer");
+    if (!boundary_loss_extents_ok(n, c, v)) return fail("seg_boundary_loss: classes must be 1..16, batch and volume non-empty");
+    if (first_class < 0 || first_class >= c) return fail("seg_boundary_loss: first_class must be 0..c-1");
+    if (!std::isfinite(grad_scale)) return fail("seg_boundary_loss: grad_scale must be finite");
+    launch_boundary_loss(logits, dist, n, c, v, first_class, grad_scale, ws, out1, dlogits, (hipStream_t)stream);
+    return SEG_OK("seg_boundary_loss");
+}
+
 }  // extern "C"
 namespace segi {
 // riders: the overflow flag was cleared and the step counter will be advanced by StepRiders of neighbouring launches (seg_train_step)

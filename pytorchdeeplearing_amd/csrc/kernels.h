@@ -339,6 +339,14 @@ void launch_cc_filter(const unsigned char* mask, unsigned char* out, int n, int 
 size_t morph3d_ws_bytes(int n, int d, int h, int w);
 void launch_morph3d(const unsigned char* mask, unsigned char* out, int n, int d, int h, int w, int cls, int op, int shape, int rz, int ry, int rx, int border,
                     int fg_value, void* ws, hipStream_t s);
+// exact Euclidean distance transform of n uint8 volumes and the boundary loss on its maps (edt.hip); modes, the no-boundary rule, out_stride_n and the
+// workspaces as documented at seg_edt / seg_boundary_loss in include/segengine.h.  Spacings already rounded to f32.
+size_t edt_ws_bytes(int n, int d, int h, int w);
+void launch_edt(const unsigned char* labels, int n, int d, int h, int w, int cls, float sz, float sy, float sx, int mode, void* ws, float* out,
+                long long out_stride_n, hipStream_t s);
+size_t boundary_loss_ws_bytes();
+void launch_boundary_loss(const float* logits, const float* dist, int n, int c, long long v, int first_class, float grad_scale, void* ws, float* out1,
+                          float* dlogits, hipStream_t s);
 // out[c] += sum_m x[m][c]   (bias gradient of a conv without GroupNorm)
 void launch_colsum(const void* x, float* out, long long M, int C, int dtype, hipStream_t s);
 

@@ -249,3 +249,74 @@ class LovaszLoss(nn.Module):
         v = logits.numel() // (n * c)
         assert target.numel() == n * v, "target must have one label per voxel"
         return _LovaszFn.apply(logits.reshape(n, c, v), target.reshape(n, v), n, c, v)
+
+
+class _BoundaryFn(torch.autograd.Function):
+    """seg_boundary_loss: the mean of p * dist over the planes >= first_class and its gradient to the logits from one pass"""
+
+    @staticmethod
+    def forward(ctx, logits, dist, first_class):
+        lg = logits.float().contiguous()
+        n, c = lg.shape[0], lg.shape[1]
+        v = lg.numel() // (n * c)
+        phi = dist.to(device=lg.device, dtype=torch.float32).contiguous()
+        assert phi.numel() == lg.numel(), "the distance maps must have the logits' shape"
+        lib = _capi.lib_for(lg.device)
+        nbytes = lib.seg_boundary_loss_ws_bytes(n, c, v)
+        lib.check(nbytes, "seg_boundary_loss_ws_bytes")
+        ws = aligned_empty(nbytes, lg.device)
+        out1 = torch.zeros(4, dtype=torch.float32, device=lg.device)
+        dx = torch.empty_like(lg)
+        lib.check(lib.seg_boundary_loss(lg.data_ptr(), phi.data_ptr(), n, c, v, first_class, 1.0, ws.data_ptr(), out1.data_ptr(), dx.data_ptr(),
+                                        _capi.stream_for(lg.device)), "seg_boundary_loss")
+        ctx.dx, ctx.in_dtype, ctx.in_shape = dx, logits.dtype, logits.shape
+        return out1[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        return (ctx.dx * g).to(ctx.in_dtype).reshape(ctx.in_shape), None, None
+
+
+def _spatial_labels(logits, target):
+    """target with one label per voxel of the logits -> (N, *spatial)"""
+    n, c = logits.shape[0], logits.shape[1]
+    assert logits.dim() in (4, 5), "logits must be (N, C, H, W) or (N, C, D, H, W)"
+    assert target.numel() * c == logits.numel(), "target must have one label per voxel"
+    return target.reshape((n,) + tuple(logits.shape[2:]))
+
+
+class BinaryBoundaryLoss(nn.Module):
+    """Boundary loss of Kervadec et al. ("Boundary loss for highly unbalanced segmentation") for a one-channel head: mean(sigmoid(logits) * phi), phi the
+    map edt(~m) * [~m] - (edt(m) - 1) * [m] of m = (target != 0) with the voxel spacing `sampling`, built on the device (prepost.boundary_distance_maps)
+    unless the caller hands it in as `dist_maps` (N, 1, *spatial).  A sample without foreground (or without background) contributes nothing.  Meant to
+    be added to a region loss by the caller: dice + alpha * boundary."""
+
+    def __init__(self, sampling=None):
+        super().__init__()
+        self.sampling = sampling
+
+    def forward(self, logits, target, dist_maps=None):
+        assert logits.shape[1] == 1, "BinaryBoundaryLoss needs a one-channel prediction"
+        if dist_maps is None:
+            from .prepost import boundary_distance_maps
+            with torch.no_grad():
+                dist_maps = boundary_distance_maps((_spatial_labels(logits, target) != 0).to(torch.uint8), 1, self.sampling)
+        return _BoundaryFn.apply(logits, dist_maps, 0)
+
+
+class MutilBoundaryLoss(nn.Module):
+    """The multi-class form: mean over the planes k >= 1 (k >= 0 with include_background) of softmax(logits)_k * phi_k, phi_k the map of (target == k):
+    SurfaceLoss with idc = the selected classes.  target: integer labels (N, *spatial); dist_maps: None or (N, C, *spatial)."""
+
+    def __init__(self, sampling=None, include_background=False):
+        super().__init__()
+        self.sampling, self.include_background = sampling, include_background
+
+    def forward(self, logits, target, dist_maps=None):
+        c = logits.shape[1]
+        assert c > 1, "MutilBoundaryLoss needs more than one class"
+        if dist_maps is None:
+            from .prepost import boundary_distance_maps
+            with torch.no_grad():
+                dist_maps = boundary_distance_maps(_spatial_labels(logits, target).to(torch.uint8), c, self.sampling)
+        return _BoundaryFn.apply(logits, dist_maps, 0 if self.include_background else 1)

@@ -357,3 +357,73 @@ def binary_morphology(mask, op, radius, shape="ball", border=None, fg_value=1, c
     lib.check(lib.seg_morph3d(mask.data_ptr(), out.data_ptr(), *nd, _pp_cls(cls), MORPH_OPS[op], SE_SHAPES[shape], *r, -1 if border is None else int(border),
                               int(fg_value), ws.data_ptr(), _capi.stream_for(mask.device)), "seg_morph3d")
     return out
+
+
+# ---- exact Euclidean distance transform and the maps of the boundary loss, csrc/edt.hip ----
+
+EDT_SQUARED, EDT_DISTANCE, EDT_SIGNED, EDT_BOUNDARY = 0, 1, 2, 3
+
+
+def _edt_sampling(sampling, rank=3):
+    """None, a scalar or one spacing per spatial axis -> (sz, sy, sx); a 2-D grid is the d = 1 volume"""
+    if sampling is None:
+        return (1.0, 1.0, 1.0)
+    s = (float(sampling),) * rank if np.isscalar(sampling) else tuple(float(v) for v in sampling)
+    if len(s) != rank:
+        raise ValueError("sampling must be a scalar or one spacing per spatial axis (%d)" % rank)
+    return (1.0,) * (3 - rank) + s
+
+
+def _edt_call(lib, mask, nd, cls, sampling, mode, out_ptr, out_stride):
+    nbytes = lib.seg_edt_ws_bytes(*nd)
+    lib.check(nbytes, "seg_edt_ws_bytes")
+    ws = _pp_workspace(mask.device, nbytes)
+    lib.check(lib.seg_edt(mask.data_ptr(), *nd, cls, *sampling, mode, ws.data_ptr(), out_ptr, out_stride, _capi.stream_for(mask.device)), "seg_edt")
+
+
+def _edt(mask, sampling, cls, mode, out):
+    mask, nd = _pp_mask(mask)
+    if out is None:
+        out = torch.empty(mask.shape, dtype=torch.float32, device=mask.device)
+    elif out.dtype != torch.float32 or out.shape != mask.shape or out.device != mask.device or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of the mask's shape on its device")
+    _edt_call(_capi.lib_for(mask.device), mask, nd, _pp_cls(cls), _edt_sampling(sampling), mode, out.data_ptr(), nd[1] * nd[2] * nd[3])
+    return out
+
+
+def distance_transform_edt(mask, sampling=None, cls=None, squared=False, out=None):
+    """scipy.ndimage.distance_transform_edt on the device: for every voxel equal to `cls` (None: non-zero) of a uint8 (D, H, W) or (N, D, H, W) tensor the
+    exact Euclidean distance (squared=True: its square) to the nearest other voxel of the same sample, 0 elsewhere; `sampling` a scalar or (sz, sy, sx).
+    float32 of the mask's shape.  A sample without any background voxel gives +inf everywhere (scipy leaves that case unspecified)."""
+    return _edt(mask, sampling, cls, EDT_SQUARED if squared else EDT_DISTANCE, out)
+
+
+def signed_distance_map(mask, sampling=None, cls=None, out=None):
+    """+ distance to the foreground outside the mask, - distance to the background inside; all zero for a sample whose mask is empty or full"""
+    return _edt(mask, sampling, cls, EDT_SIGNED, out)
+
+
+def boundary_distance_maps(labels, num_class, sampling=None, out=None):
+    """The maps of the boundary loss (Kervadec et al.), edt(~m) * [~m] - (edt(m) - 1) * [m] per class: labels (N, *spatial) with two or three spatial axes
+    -> float32 (N, C, *spatial), C = num_class.  num_class == 1: one plane for labels != 0; otherwise plane k for labels == k, k = 0..C-1.  A plane whose
+    mask is empty or full in a sample is zero there.  One seg_edt call per class on the current stream, written in place, no synchronisation."""
+    if not torch.is_tensor(labels) or labels.dim() not in (3, 4) or labels.dtype.is_floating_point or labels.dtype.is_complex:
+        raise TypeError("expected an integer label tensor (N, H, W) or (N, D, H, W)")
+    num_class = int(num_class)
+    if num_class < 1 or num_class > 256:
+        raise ValueError("num_class must be 1..256")
+    lab = labels if labels.dtype == torch.uint8 else labels.to(torch.uint8)
+    lab = lab.contiguous()
+    spatial = tuple(lab.shape[1:])
+    nd = (lab.shape[0],) + (1,) * (3 - len(spatial)) + spatial
+    v = nd[1] * nd[2] * nd[3]
+    shape = (lab.shape[0], num_class) + spatial
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=lab.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or out.device != lab.device or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor (N, num_class, *spatial) on the labels' device")
+    lib = _capi.lib_for(lab.device)
+    sp = _edt_sampling(sampling, len(spatial))
+    for k in range(num_class):
+        _edt_call(lib, lab, nd, -1 if num_class == 1 else k, sp, EDT_BOUNDARY, out.data_ptr() + 4 * k * v, num_class * v)
+    return out
